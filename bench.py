@@ -39,11 +39,21 @@ value = T cameras' pixels / step time.  At N > 1 the weak headline is
 followed by the same measurement of the 27-camera split step, reported as
 `split_step` (so one driver run gives both curves).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line (rank 0).  Besides the contract fields it carries
+Prints ONE JSON line (rank 0).  A plain run does what the headline needs and
+no more: set-up, W warm-up steps and the one untimed step that `--full` times
+per stage (so both kinds of run time the same steps), K timed steps, the line
+with the contract
+fields (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`)
+and the run's `config`.  `--dump-outputs DIR`: after the timed steps, one more
+step of the timed path from the seeded parameters the run started with, and
+what it computed written to DIR (dump_outputs).  Everything else is measured
+only with `--full`: the per-stage timing and the instance counts, the
+other call pattern, the split step and the CPU legs.  With `--full` the line
+also carries
 `roofline` (dominant kernel, live HIP-event timing over the timed region),
 `cpu_baseline` (north star's naive pure-PyTorch fp32 CPU splat, fwd + autograd
 bwd, on a bounded tile sample of camera 0, on the host's cores; the
@@ -107,7 +117,15 @@ def parse():
     ap.add_argument("--height", type=int, default=800)
     ap.add_argument("--features", type=int, default=32)
     ap.add_argument("--compat", default="reference", choices=["reference", "fixed"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without its CPU legs")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: per-stage timing and the roofline of the dominant kernel, instance "
+                         "counts, the other call pattern, the split step, the CPU baselines and the PSNR legs")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps: one more step of the timed path from the seeded parameters the run "
+                         "started with (the same inputs every run); rank 0 writes what it computed to "
+                         "DIR/<name>.npy (float32): the rendered images, depths, features and radii and the "
+                         "parameters' gradients; arrays above their share of 48 MB as a fixed seeded sample")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--dump-params", default="",
                     help="rank 0 writes the parameters after the timed steps to this .npz (rehearsal checks)")
@@ -457,6 +475,42 @@ def calc_psnr(img1, img2):
         return float(np.mean(20 * np.log10(1.0 / np.sqrt(mse))))
 
 
+DUMP_BUDGET_BYTES = 48 << 20  # all of --dump-outputs' files together (float32 elements)
+
+
+def dump_outputs(path, calls, params, seed, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: what one step of the timed path handed its caller, as
+    path/<name>.npy (float32, flattened).  `calls` are the step's rasterizer
+    calls in order ({image, radii, depth, feature}: one camera batch, or one
+    entry per camera of the per-camera drop-in); their outputs are joined
+    along the camera axis.  Beside them the gradient the step left on every
+    parameter (grad_<name>, where the step binds one).  The parameters after
+    the optimizer step are not written: Adam's moments come from the timed
+    steps, whose gradients differ from run to run by the float atomics' order,
+    so its update of the restored parameters is not the same every run.  Every
+    array gets the same share of `budget`; a larger one is written as a
+    sample of its elements at sorted indices drawn from a generator seeded by
+    (seed, the array's position), so two runs with the same arguments write
+    the same elements."""
+    arrays = {}
+    for name in ("image", "depth", "feature", "radii"):
+        parts = [c[name] if c[name].dim() == 4 or name == "radii" and c[name].dim() == 2 else c[name][None]
+                 for c in calls if c[name] is not None]
+        if parts:
+            arrays[name] = torch.cat([p.detach() for p in parts])
+    for k, v in params.items():
+        if v.grad is not None:
+            arrays["grad_" + k] = v.grad.detach()
+    os.makedirs(path, exist_ok=True)
+    share = budget // 4 // len(arrays)
+    for i, (name, t) in enumerate(arrays.items()):
+        flat = t.reshape(-1)
+        if flat.numel() > share:
+            idx = np.sort(np.random.default_rng([seed, i]).integers(0, flat.numel(), share))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        np.save(os.path.join(path, name + ".npy"), flat.float().cpu().numpy())
+
+
 def host_cores():
     """The host cores this process may use: the scheduler's affinity set,
     capped by OMP_NUM_THREADS when set (the GPU box exports its CPU share
@@ -752,9 +806,8 @@ def main():
     # The parameters train during the run (Adam on fixed synthetic upstream
     # gradients), so the scene the kernels render drifts from step to step:
     # the counts are taken before the timed steps and again after them, and
-    # the byte model uses their mean.
-    inst0 = instance_counts()
-    inst = inst0
+    # the byte model uses their mean.  (--full: 27 forwards of their own)
+    inst0 = instance_counts() if args.full else None
 
     # 4 = the box's hardware queues per process (GPU_MAX_HW_QUEUES): measured
     # 822 / 846 / 871 / 912 / 888 Mpix/s at 1 / 2 / 3 / 4 / 6 streams
@@ -789,14 +842,24 @@ def main():
 
     batch_parts = batch_inputs(settings, args.sub_batches)
 
+    # --dump-outputs: the rasterizer calls of the last timed step leave what
+    # they returned here (one entry per call: a camera batch or one camera)
+    last = {"on": False, "calls": []}
+
+    def keep(im, radius, depth, feat=None):
+        if last["on"]:
+            last["calls"].append({"image": im, "radii": radius, "depth": depth, "feature": feat})
+
     def run_part(ras, ups, rv, ready=None, grad_into=None):
         up_c, up_d, up_f = ups
         if up_f is not None:  # G3 call (label + semantic_feature)
             im, radius, feat, depth, _ = ras(**rv, feature_ready=ready, grad_into=grad_into)
             torch.autograd.backward([im, depth, feat], [up_c, up_d, up_f])
+            keep(im, radius, depth, feat)
         else:                 # G2 call (label only)
             im, radius, depth, _ = ras(**rv, grad_into=grad_into)
             torch.autograd.backward([im, depth], [up_c, up_d])
+            keep(im, radius, depth)
 
     # the raw parameters' GaussianRasterizer argument names (raw_rendervar)
     arg_of = {"means3D": "means3D", "rgb_colors": "colors_precomp", "unnorm_rotations": "rotations",
@@ -930,11 +993,13 @@ def main():
         rv = params2rendervar(params, label)
         ras = GaussianRasterizer(settings[0])
         if up_feat is not None:
-            im, _, feat, depth, _ = ras(**rv)
+            im, radius, feat, depth, _ = ras(**rv)
             torch.autograd.backward([im, depth, feat], [up_color, up_depth, up_feat])
+            keep(im, radius, depth, feat)
         else:
-            im, _, depth, _ = ras(**rv)
+            im, radius, depth, _ = ras(**rv)
             torch.autograd.backward([im, depth], [up_color, up_depth])
+            keep(im, radius, depth)
         if zero:
             zs.finish(inline=True)
             return
@@ -988,6 +1053,7 @@ def main():
                     outs.append(feat)
                     grads.append(up_feat)
                 torch.autograd.backward(outs, grads)
+                keep(im, radius, depth, feat if up_feat is not None else None)
         for st in streams:
             main.wait_stream(st)
         summed = sink.gradients() if sink is not None else {k: v.grad for k, v in leaves.items()}
@@ -1007,19 +1073,26 @@ def main():
         step()
     # one untimed step with every stage timed: the per-stage breakdown and the
     # dominant kernel; the timed region then records events around that kernel
-    # only (each timed stage costs an event pair on the stream)
+    # only (each timed stage costs an event pair on the stream).  The stage
+    # timing is --full's; the step itself runs in a plain run too, without
+    # events in it or in the timed steps, so the timed steps are the same
+    # optimizer steps W + 2 .. W + 1 + K with and without --full (and leave
+    # the same parameters).
     torch.cuda.synchronize()
-    _lib.timing_enable(True)
+    if args.full:
+        _lib.timing_enable(True)
     step()
-    all_stages = _lib.timing_read()
-    _lib.timing_enable(False)
-    stage_ms = {k: v[0] for k, v in all_stages.items()}
-    dom = max(stage_ms, key=stage_ms.get)
+    if args.full:
+        all_stages = _lib.timing_read()
+        _lib.timing_enable(False)
+        stage_ms = {k: v[0] for k, v in all_stages.items()}
+        dom = max(stage_ms, key=stage_ms.get)
     torch.cuda.synchronize()
     if dist_on:
         dist.barrier()
     torch.cuda.synchronize()
-    _lib.timing_enable(True, stages=[dom])
+    if args.full:
+        _lib.timing_enable(True, stages=[dom])
 
     def plan_counts():
         """(forward calls, capacity retries) of the camera batch's sync-free plans."""
@@ -1037,11 +1110,13 @@ def main():
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     plan1 = plan_counts()
-    stages = _lib.timing_read()
-    _lib.timing_enable(False)
+    if args.full:
+        stages = _lib.timing_read()
+        _lib.timing_enable(False)
     drain()
-    inst1 = instance_counts()
-    inst = [tuple((a + b) / 2 for a, b in zip(x, y)) for x, y in zip(inst0, inst1)]
+    if args.full:
+        inst1 = instance_counts()
+        inst = [tuple((a + b) / 2 for a, b in zip(x, y)) for x, y in zip(inst0, inst1)]
     if args.dump_params and rank == 0:
         drain()
         torch.cuda.synchronize()
@@ -1053,7 +1128,8 @@ def main():
 
     # the other call pattern on the same scene, timed the same way (reported
     # beside the headline: the per-camera drop-in or the camera batch)
-    other = other_mode(args.mode, my_windows is not None, strong, world, os.environ.get("GS_BENCH_OTHER") != "0")
+    other = other_mode(args.mode, my_windows is not None, strong, world,
+                       args.full and os.environ.get("GS_BENCH_OTHER") != "0")
     for _ in range(args.warmup if other else 0):
         step(other)
     torch.cuda.synchronize()
@@ -1101,7 +1177,7 @@ def main():
                      "balancing the ranks' tile-list instances (distributed.shard_camera_windows)"
                      if args.split == "windows" else
                      "camera c on rank c mod N (distributed.shard_cameras)")
-    if not strong and args.mode == "batch":
+    if args.full and not strong and args.mode == "batch":
         n_split = args.cams
         if world > 1:
             rig_s = camera_rig(n_split, args.width, args.height, seed=args.seed)
@@ -1124,6 +1200,28 @@ def main():
                  "value": round(n_split * W_ * H_ / 1e6 / (ms_s / 1e3), 3), "unit": "Mpix/s",
                  "scaling": "strong", "sharding": sharding_note}
 
+    # --dump-outputs: the parameters the timed steps leave differ from run to
+    # run (the backward's float atomics sum in another order every run, and
+    # the Adam steps on fixed upstream gradients amplify that), so the step
+    # that is written is one more step of the timed path, untimed, from the
+    # seeded parameters the run started with: the same inputs every run and in
+    # every build.  Every rank takes it (its collectives); rank 0 writes.
+    if args.dump_outputs:
+        drain()
+        torch.cuda.synchronize()  # every stream of the earlier steps is done with the parameters
+        with torch.no_grad():
+            for k_, v_ in params.items():
+                v_.copy_(params0[k_])
+        torch.cuda.synchronize()
+        last["on"] = True
+        step()
+        last["on"] = False
+        drain()
+        torch.cuda.synchronize()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, last["calls"], params, args.seed)
+        last["calls"] = []
+
     ms_per_step = elapsed / args.steps * 1e3
     n_cams_total = args.cams_total if strong else world * args.cams
     mpix_total = n_cams_total * W_ * H_ / 1e6
@@ -1135,44 +1233,46 @@ def main():
         mpix_total = share * W_ * H_ / 1e6
     value = mpix_total / (ms_per_step / 1e3)
 
-    # roofline of the dominant stage (live HIP-event durations over the timed region)
-    cams_per_launch = len(batch_parts[0][0].settings_list) if args.mode == "batch" else 1
-    per_cam_bytes = [stage_bytes(L, Pv, args.gaussians, W_, H_, args.features, args.compat, cams_per_launch)
-                     for L, Pv, _ in inst]
-    launches = stages[dom][1]
-    alg_bytes_total = sum(b[dom] for b in per_cam_bytes) * args.steps
-    avg_ms = stages[dom][0] / max(launches, 1)
-    alg_per_launch = alg_bytes_total / max(launches, 1)
-    achieved = alg_per_launch / (avg_ms / 1e3) / 1e9 if avg_ms > 0 else 0.0
-    # the PMC-derived views only for the workload the counters were measured on
-    workload = {"gaussians": args.gaussians, "width": W_, "height": H_, "features": args.features,
-                "compat": args.compat, "rig": len(rig), "cams_per_launch": cams_per_launch, "seed": args.seed}
-    pmc = pmc_for(workload) if args.mode == "batch" and world == 1 else {}
-    meas = (pmc.get("traffic") or {}).get("bytes_per_camera", {})
-    hbm = {"achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-           "frac": round(achieved / HBM_PEAK_GBS, 4),
-           "traffic": int(meas[dom] * cams_per_launch) if dom in meas else None}
-    issue = issue_view(pmc, dom, avg_ms, cams_per_launch)
-    atomics = atomic_view(pmc, dom, avg_ms, cams_per_launch)
-    # the binding roof: the highest of the HBM (algorithmic bytes), float-atomic
-    # and issue fractions of the dominant kernel
-    roofs = {"hbm": hbm}
-    if atomics:
-        roofs["atomics"] = atomics
-    if issue:
-        roofs["issue"] = issue
-    bound = max(roofs, key=lambda r: roofs[r]["frac"])
-    b = roofs[bound]
-    if bound == "issue":
-        b = {"achieved": b["frac"], "peak": 1.0, "unit": "fraction of SIMD issue cycles", "frac": b["frac"]}
-    roofline = {"bound": bound, "achieved": b["achieved"], "peak": b["peak"], "unit": b["unit"], "frac": b["frac"],
-                "traffic": hbm["traffic"], "kernel": dom, "avg_launch_ms": round(avg_ms, 4),
-                "alg_bytes_per_launch": int(alg_per_launch), "cams_per_launch": cams_per_launch,
-                "hbm": hbm, "atomics": atomics, "issue": issue,
-                "pmc_workload_matched": bool(pmc),
-                "stages": stage_table(stage_ms, {k: np.mean([pb[k] for pb in per_cam_bytes])
-                                                 for k in per_cam_bytes[0]}, pmc,
-                                      len(my_cams))}
+    roofline = None
+    if args.full:
+        # roofline of the dominant stage (live HIP-event durations over the timed region)
+        cams_per_launch = len(batch_parts[0][0].settings_list) if args.mode == "batch" else 1
+        per_cam_bytes = [stage_bytes(L, Pv, args.gaussians, W_, H_, args.features, args.compat, cams_per_launch)
+                         for L, Pv, _ in inst]
+        launches = stages[dom][1]
+        alg_bytes_total = sum(b[dom] for b in per_cam_bytes) * args.steps
+        avg_ms = stages[dom][0] / max(launches, 1)
+        alg_per_launch = alg_bytes_total / max(launches, 1)
+        achieved = alg_per_launch / (avg_ms / 1e3) / 1e9 if avg_ms > 0 else 0.0
+        # the PMC-derived views only for the workload the counters were measured on
+        workload = {"gaussians": args.gaussians, "width": W_, "height": H_, "features": args.features,
+                    "compat": args.compat, "rig": len(rig), "cams_per_launch": cams_per_launch, "seed": args.seed}
+        pmc = pmc_for(workload) if args.mode == "batch" and world == 1 else {}
+        meas = (pmc.get("traffic") or {}).get("bytes_per_camera", {})
+        hbm = {"achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+               "frac": round(achieved / HBM_PEAK_GBS, 4),
+               "traffic": int(meas[dom] * cams_per_launch) if dom in meas else None}
+        issue = issue_view(pmc, dom, avg_ms, cams_per_launch)
+        atomics = atomic_view(pmc, dom, avg_ms, cams_per_launch)
+        # the binding roof: the highest of the HBM (algorithmic bytes), float-atomic
+        # and issue fractions of the dominant kernel
+        roofs = {"hbm": hbm}
+        if atomics:
+            roofs["atomics"] = atomics
+        if issue:
+            roofs["issue"] = issue
+        bound = max(roofs, key=lambda r: roofs[r]["frac"])
+        b = roofs[bound]
+        if bound == "issue":
+            b = {"achieved": b["frac"], "peak": 1.0, "unit": "fraction of SIMD issue cycles", "frac": b["frac"]}
+        roofline = {"bound": bound, "achieved": b["achieved"], "peak": b["peak"], "unit": b["unit"], "frac": b["frac"],
+                    "traffic": hbm["traffic"], "kernel": dom, "avg_launch_ms": round(avg_ms, 4),
+                    "alg_bytes_per_launch": int(alg_per_launch), "cams_per_launch": cams_per_launch,
+                    "hbm": hbm, "atomics": atomics, "issue": issue,
+                    "pmc_workload_matched": bool(pmc),
+                    "stages": stage_table(stage_ms, {k: np.mean([pb[k] for pb in per_cam_bytes])
+                                                     for k in per_cam_bytes[0]}, pmc,
+                                          len(my_cams))}
 
     result = {
         "metric": METRIC, "value": round(value, 3), "unit": "Mpix/s", "n_gpus": world,
@@ -1228,17 +1328,24 @@ def main():
                                      "one all-reduce before Adam" if world > 1 else
                                      "none (one rank); the feature Adam step overlapped with the next step's "
                                      "projection and binning" if local_overlap else "none (one rank)")},
-        "roofline": roofline,
-        "stages_ms_per_step": {k: round(v, 4) for k, v in stage_ms.items()},
-        "split_step": split,
-        "other_mode": None if other is None else {
-            "mode": other, "ms_per_step": round(other_elapsed / args.steps * 1e3, 3),
-            "value": round(mpix_total / (other_elapsed / args.steps), 3),
-            "streams": n_streams if other == "percam" else 1},
-        "instances_per_cam": int(np.mean([L for L, _, _ in inst])),
-        "instances_per_cam_before_after": [int(np.mean([x[0] for x in inst0])), int(np.mean([x[0] for x in inst1]))],
-        "num_rendered_per_cam": int(np.mean([R for _, _, R in inst])),
+        "full": args.full,
     }
+    if args.full:
+        result.update({
+            "roofline": roofline,
+            "stages_ms_per_step": {k: round(v, 4) for k, v in stage_ms.items()},
+            "split_step": split,
+            "other_mode": None if other is None else {
+                "mode": other, "ms_per_step": round(other_elapsed / args.steps * 1e3, 3),
+                "value": round(mpix_total / (other_elapsed / args.steps), 3),
+                "streams": n_streams if other == "percam" else 1},
+            "instances_per_cam": int(np.mean([L for L, _, _ in inst])),
+            "instances_per_cam_before_after": [int(np.mean([x[0] for x in inst0])),
+                                               int(np.mean([x[0] for x in inst1]))],
+            "num_rendered_per_cam": int(np.mean([R for _, _, R in inst])),
+        })
+    if args.dump_outputs:
+        result["outputs_dir"] = args.dump_outputs
     if strong:
         # the split's work model: every rank's pieces and modelled load
         # (row_cost instances + PIECE_FRACTION x a mean camera per piece)
@@ -1263,7 +1370,7 @@ def main():
     if args.step_times:
         result["host_step_ms"] = [round((b - a) * 1e3, 3) for a, b in zip([t0] + host_marks, host_marks)]
         result["tail_ms"] = round((t0 + elapsed - host_marks[-1]) * 1e3, 3) if world == 1 else None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and settings[0].tile_window is None:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and settings[0].tile_window is None:
         cb, psnr, psnr_gt = cpu_baseline(args, params0, label, my_cams[0], settings[0], dev)
         result["cpu_baseline"] = cb
         result["psnr_vs_oracle_db"] = round(psnr, 2) if np.isfinite(psnr) else "inf"

@@ -11,9 +11,9 @@ for rep in $(seq 1 ${REPS:-2}); do
 for e in ${ENVS:--}; do
   n=$(echo "$e" | tr '=' '_')
   if [ "$e" = "-" ]; then
-    timeout -k 10 200 python bench.py --no-cpu-baseline ${BENCH_ARGS:-} > $O/b_${n}_$rep.json 2> $O/b_${n}_$rep.err || { tail -5 $O/b_${n}_$rep.err; exit 1; }
+    timeout -k 10 200 python bench.py --full --no-cpu-baseline ${BENCH_ARGS:-} > $O/b_${n}_$rep.json 2> $O/b_${n}_$rep.err || { tail -5 $O/b_${n}_$rep.err; exit 1; }
   else
-    env "$e" timeout -k 10 200 python bench.py --no-cpu-baseline ${BENCH_ARGS:-} > $O/b_${n}_$rep.json 2> $O/b_${n}_$rep.err || { tail -5 $O/b_${n}_$rep.err; exit 1; }
+    env "$e" timeout -k 10 200 python bench.py --full --no-cpu-baseline ${BENCH_ARGS:-} > $O/b_${n}_$rep.json 2> $O/b_${n}_$rep.err || { tail -5 $O/b_${n}_$rep.err; exit 1; }
   fi
   python -c "import json; d=json.load(open('$O/b_${n}_$rep.json')); print('bench', '$n', d['value'], d['ms_per_step'], {k: round(v,3) for k, v in d['stages_ms_per_step'].items() if v > 0.04})"
 done

@@ -7,7 +7,7 @@ R=$GRAFT_REPO_ROOT
 cd $R
 O=$R/gpurun_out/${TAG:-local_overlap}
 mkdir -p $O
-A="--steps 3 --warmup 1 --gaussians 100000 --cams 4 --width 400 --height 400 --no-cpu-baseline"
+A="--steps 3 --warmup 1 --gaussians 100000 --cams 4 --width 400 --height 400 --full --no-cpu-baseline"
 env GS_BENCH_OVERLAP=1 timeout -k 10 200 python bench.py $A --dump-params $O/l1.npz > $O/l1.json 2> $O/l1.err || { tail $O/l1.err; exit 1; }
 env GS_BENCH_OVERLAP=0 timeout -k 10 200 python bench.py $A --dump-params $O/l0a.npz > $O/l0a.json 2> $O/l0a.err || exit 1
 env GS_BENCH_OVERLAP=0 timeout -k 10 200 python bench.py $A --dump-params $O/l0b.npz > $O/l0b.json 2> $O/l0b.err || exit 1

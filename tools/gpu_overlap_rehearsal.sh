@@ -21,7 +21,7 @@ GS_BENCH_SHARE_GPU=1 timeout -k 10 300 python -m torch.distributed.run --nnodes=
   --master-addr 127.0.0.1 --master-port 29560 tools/zov_check.py > $O/zov_check.json 2> $O/zov_check.err \
   || { tail -20 $O/zov_check.err; cat $O/zov_check.json; exit 1; }
 python -c "import json; d=json.load(open('$O/zov_check.json')); print('zov_check ok:', d['ok'], 'max grad rel:', max(max(r.values()) for x in d['ranks'] for r in x['grad_rel']))"
-A="--gpus 2 --steps 3 --warmup 1 --gaussians 100000 --cams 4 --width 400 --height 400 --no-cpu-baseline"
+A="--gpus 2 --steps 3 --warmup 1 --gaussians 100000 --cams 4 --width 400 --height 400 --full --no-cpu-baseline"
 run() {  # name, port, extra env
   env GS_BENCH_BACKEND=gloo GS_BENCH_SHARE_GPU=1 $3 timeout -k 10 300 python -m torch.distributed.run --nnodes=1 \
     --nproc-per-node 2 --master-addr 127.0.0.1 --master-port $2 bench.py $A --dump-params $O/$1.npz \

@@ -13,7 +13,7 @@ for rep in 1 2 3; do
       cams4) env="GS_BENCH_OTHER=0"; a="--cams 4";;
     esac
     f=$O/${v}_$rep.json
-    env $env timeout -k 10 200 python bench.py $a --no-cpu-baseline > $f 2> ${f%.json}.err || { tail -5 ${f%.json}.err; exit 1; }
+    env $env timeout -k 10 200 python bench.py $a --full --no-cpu-baseline > $f 2> ${f%.json}.err || { tail -5 ${f%.json}.err; exit 1; }
     python -c "import json; d=json.load(open('$f')); print('$v', $rep, d['ms_per_step'], d['config']['cams_per_rank'])"
   done
 done

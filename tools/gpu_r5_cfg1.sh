@@ -4,7 +4,7 @@
 set -o pipefail
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/${TAG:-r05c1}; mkdir -p $O
-A="--gaussians 100000 --cams 1 --steps ${STEPS:-200} --warmup 20 --no-cpu-baseline"
+A="--gaussians 100000 --cams 1 --steps ${STEPS:-200} --warmup 20 --full --no-cpu-baseline"
 for rep in 1 2; do
   for v in percam batch_sf batch_2p; do
     case $v in

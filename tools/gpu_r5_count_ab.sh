@@ -15,7 +15,7 @@ for rep in 1 2 3; do
     for cfg in bench cfg4; do
       a=""; [ $cfg = cfg4 ] && a="$C4"
       f=$O/${cfg}_${v}_$rep.json
-      env GS_BENCH_OTHER=0 $env timeout -k 10 300 python bench.py $a --no-cpu-baseline > $f 2> ${f%.json}.err || { tail -5 ${f%.json}.err; exit 2; }
+      env GS_BENCH_OTHER=0 $env timeout -k 10 300 python bench.py $a --full --no-cpu-baseline > $f 2> ${f%.json}.err || { tail -5 ${f%.json}.err; exit 2; }
       python -c "import json; d=json.load(open('$f')); s=d['stages_ms_per_step']; print('$cfg $v', $rep, d['ms_per_step'], s['scan'], s['duplicate'], d['config']['binning_walk'][:8])"
     done
   done

@@ -7,7 +7,7 @@ O=gpurun_out/${TAG:-r05d2}; mkdir -p $O
 run() {  # name, port, extra args
   local t0=$(date +%s)
   GS_BENCH_TRACEBACKS=${TB:-60} GS_BENCH_BACKEND=gloo GS_BENCH_SHARE_GPU=1 timeout -k 10 ${LIMIT:-500} python -m torch.distributed.run --nnodes=1 \
-    --nproc-per-node 2 --master-addr 127.0.0.1 --master-port $2 bench.py --gpus 2 --steps 3 --warmup 1 $3 \
+    --nproc-per-node 2 --master-addr 127.0.0.1 --master-port $2 bench.py --gpus 2 --steps 3 --warmup 1 --full $3 \
     > $O/$1.json 2> $O/$1.err &
   local pid=$!
   while kill -0 $pid 2>/dev/null; do sleep 30; echo "$1: $(( $(date +%s) - t0 )) s"; done

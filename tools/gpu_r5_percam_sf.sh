@@ -14,10 +14,10 @@ for rep in 1 2; do
   for v in 0 1; do
     f=$O/cfg1_sf${v}_$rep.json
     GS_BENCH_OTHER=0 GS_PERCAM_SYNC_FREE=$v timeout -k 10 200 python bench.py --mode percam --gaussians 100000 \
-      --cams 1 --steps 200 --warmup 20 --no-cpu-baseline > $f 2> ${f%.json}.err || { tail -5 ${f%.json}.err; exit 2; }
+      --cams 1 --steps 200 --warmup 20 --full --no-cpu-baseline > $f 2> ${f%.json}.err || { tail -5 ${f%.json}.err; exit 2; }
     python -c "import json; d=json.load(open('$f')); print('cfg1 percam sf=$v', $rep, d['ms_per_step'])"
     f=$O/bench_sf${v}_$rep.json
-    GS_BENCH_OTHER=0 GS_PERCAM_SYNC_FREE=$v timeout -k 10 200 python bench.py --mode percam --no-cpu-baseline \
+    GS_BENCH_OTHER=0 GS_PERCAM_SYNC_FREE=$v timeout -k 10 200 python bench.py --mode percam --full --no-cpu-baseline \
       > $f 2> ${f%.json}.err || { tail -5 ${f%.json}.err; exit 3; }
     python -c "import json; d=json.load(open('$f')); print('27cam percam sf=$v', $rep, d['ms_per_step'])"
   done

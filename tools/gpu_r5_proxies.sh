@@ -13,13 +13,13 @@ cd $R
 TAG=${TAG:-r05px}
 O=$R/gpurun_out/$TAG
 mkdir -p $O
-timeout -k 10 300 python bench.py --no-cpu-baseline > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 1; }
+timeout -k 10 300 python bench.py --full --no-cpu-baseline > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 1; }
 python -c "import json; d=json.load(open('$O/bench.json')); print('bench', d['value'], d['ms_per_step'])"
 WS=""
 for rep in $(seq 1 ${REPS:-3}); do
 for r in ${RANKS:-0 1 2 3 4 5 6 7}; do
   f=$O/proxy_r${r}_$rep.json
-  timeout -k 10 200 python bench.py --cams-total 27 --proxy-world ${N:-8} --proxy-rank $r --no-cpu-baseline \
+  timeout -k 10 200 python bench.py --cams-total 27 --proxy-world ${N:-8} --proxy-rank $r --full --no-cpu-baseline \
     --steps ${STEPS:-20} --warmup ${WARMUP:-3} ${WS:+--whole-scale $WS} ${BENCH_ARGS:-} > $f 2> ${f%.json}.err || { tail -5 ${f%.json}.err; exit 2; }
   python -c "import json; d=json.load(open('$f')); m=d['split_model']['ranks'][$r]; print('proxy', $r, $rep, d['ms_per_step'], m['pieces'], m['model_load'])"
   if [ -z "$WS" ]; then

@@ -17,7 +17,7 @@ for rep in 1 2 3; do
     for cfg in bench px5; do
       a=""; [ $cfg = px5 ] && a="$PX"
       f=$O/${cfg}_${nt}_$rep.json
-      env GS_BENCH_OTHER=0 GS_SORT_SHORT_NT=$nt timeout -k 10 300 python bench.py $a --no-cpu-baseline > $f 2> ${f%.json}.err || { tail -5 ${f%.json}.err; exit 2; }
+      env GS_BENCH_OTHER=0 GS_SORT_SHORT_NT=$nt timeout -k 10 300 python bench.py $a --full --no-cpu-baseline > $f 2> ${f%.json}.err || { tail -5 ${f%.json}.err; exit 2; }
       python -c "import json; d=json.load(open('$f')); s=d['stages_ms_per_step']; print('$cfg nt=$nt', $rep, d['ms_per_step'], 'sort', s['sort'], 'dup', s['duplicate'])"
     done
   done

@@ -5,9 +5,9 @@ R=$GRAFT_REPO_ROOT
 cd $R
 O=$R/gpurun_out/${TAG:-r05steps}
 mkdir -p $O
-timeout -k 10 300 python bench.py --no-cpu-baseline --steps 200 --warmup 3 --step-times > $O/s200.json 2> $O/s200.err || { tail $O/s200.err; exit 1; }
-timeout -k 10 300 python bench.py --no-cpu-baseline > $O/d1.json 2> $O/d1.err || { tail $O/d1.err; exit 1; }
-timeout -k 10 300 python bench.py --no-cpu-baseline --steps 20 --warmup 20 > $O/w20.json 2> $O/w20.err || { tail $O/w20.err; exit 1; }
+timeout -k 10 300 python bench.py --full --no-cpu-baseline --steps 200 --warmup 3 --step-times > $O/s200.json 2> $O/s200.err || { tail $O/s200.err; exit 1; }
+timeout -k 10 300 python bench.py --full --no-cpu-baseline > $O/d1.json 2> $O/d1.err || { tail $O/d1.err; exit 1; }
+timeout -k 10 300 python bench.py --full --no-cpu-baseline --steps 20 --warmup 20 > $O/w20.json 2> $O/w20.err || { tail $O/w20.err; exit 1; }
 python - <<'PY'
 import json
 d = json.load(open("gpurun_out/${TAG:-r05steps}/s200.json".replace("${TAG:-r05steps}", __import__("os").environ.get("TAG", "r05steps"))))

@@ -11,7 +11,7 @@ for rep in $(seq 1 ${REPS:-3}); do
 for cams in 4 27; do
 for sf in 1 0; do
   f=$O/c${cams}_sf${sf}_$rep.json
-  GS_BENCH_SYNC_FREE=$sf timeout -k 10 200 python bench.py --cams $cams --no-cpu-baseline --steps 100 --warmup 10 \
+  GS_BENCH_SYNC_FREE=$sf timeout -k 10 200 python bench.py --cams $cams --full --no-cpu-baseline --steps 100 --warmup 10 \
     > $f 2> ${f%.json}.err || { tail -5 ${f%.json}.err; exit 1; }
   python -c "import json; d=json.load(open('$f')); print('cams', $cams, 'sync_free', $sf, $rep, d['ms_per_step'], d['config']['forward'][:10])"
 done

@@ -10,7 +10,7 @@ O=$R/gpurun_out/${TAG:-r05vs4}
 mkdir -p $O
 run() {  # name, dir, cams, env
   f=$O/$1.json
-  (cd $2 && env $4 timeout -k 10 200 python bench.py --cams $3 --no-cpu-baseline --steps 100 --warmup 10) \
+  (cd $2 && env $4 timeout -k 10 200 python bench.py --cams $3 --full --no-cpu-baseline --steps 100 --warmup 10) \
     > $f 2> $O/$1.err || { tail -5 $O/$1.err; exit 1; }
   python -c "import json; d=json.load(open('$f')); print('$1', d['ms_per_step'], round(d['value'], 1))"
 }

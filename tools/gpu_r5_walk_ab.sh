@@ -9,7 +9,7 @@ O=gpurun_out/${TAG:-r05wk}; mkdir -p $O
 timeout -k 10 300 python -u -m pytest -x -q --timeout 120 --timeout-method thread tests/test_gpu_walk_order.py \
   tests/test_gpu_sync_free.py > $O/tests.log 2>&1 || { tail -30 $O/tests.log; exit 1; }
 tail -1 $O/tests.log
-A="--gaussians 1000000 --width 1920 --height 1080 --cams 4 --features 32 --steps 10 --warmup 3 --no-cpu-baseline"
+A="--gaussians 1000000 --width 1920 --height 1080 --cams 4 --features 32 --steps 10 --warmup 3 --full --no-cpu-baseline"
 for rep in 1 2 3; do
   for w in 0 auto; do
     f=$O/cfg4_w${w}_$rep.json
@@ -17,5 +17,5 @@ for rep in 1 2 3; do
     python -c "import json; d=json.load(open('$f')); s=d['stages_ms_per_step']; print('cfg4 walk=$w', $rep, d['ms_per_step'], d['config']['binning_walk'][:12], s['scan'], s['duplicate'])"
   done
 done
-timeout -k 10 300 python bench.py --no-cpu-baseline > $O/bench.json 2> $O/bench.err || exit 3
+timeout -k 10 300 python bench.py --full --no-cpu-baseline > $O/bench.json 2> $O/bench.err || exit 3
 python -c "import json; d=json.load(open('$O/bench.json')); print('bench', d['value'], d['ms_per_step'], d['config']['binning_walk'])"

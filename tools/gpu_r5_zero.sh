@@ -19,7 +19,7 @@ for r in ${RANKS:-2 5}; do
 for z in 0 1; do
   f=$O/proxy_r${r}_z${z}_$rep.json
   GS_BENCH_ZERO=$z timeout -k 10 200 python bench.py --cams-total 27 --proxy-world 8 --proxy-rank $r \
-    --no-cpu-baseline --whole-scale $WS > $f 2> ${f%.json}.err || { tail -5 ${f%.json}.err; exit 2; }
+    --full --no-cpu-baseline --whole-scale $WS > $f 2> ${f%.json}.err || { tail -5 ${f%.json}.err; exit 2; }
   python -c "import json; d=json.load(open('$f')); print('proxy', $r, 'zero', $z, $rep, d['ms_per_step'], d['config']['optimizer'][:40])"
 done
 done

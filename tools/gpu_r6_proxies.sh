@@ -10,12 +10,11 @@ timeout -k 10 600 python -u -m pytest tests/test_gpu_parity.py tests/test_gpu_fu
   --timeout-method thread -p no:cacheprovider > $O/parity.log 2>&1 || { tail -30 $O/parity.log; exit 4; }
 tail -1 $O/parity.log
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/kt -o kt --output-format csv -- python3 $R/bench.py --no-cpu-baseline --steps 5 --warmup 2 > $O/kt.json 2> $O/kt.err || { tail $O/kt.err; exit 1; }
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/kt -o kt --output-format csv -- python3 $R/bench.py --full --no-cpu-baseline --steps 5 --warmup 2 > $O/kt.json 2> $O/kt.err || { tail $O/kt.err; exit 1; }
 cd $R && grep -E "absmax|render_fwd|Name" $O/kt/kt_kernel_stats.csv | cut -c1-160 | head -8
 rm -f $O/kt/kt_kernel_trace.csv
 # the other configs (configs[1] drop-in F = 0 / 32, configs[4] per rank)
-bash tools/gpu_configs.sh || exit 3
-cp gpurun_out/configs.jsonl $O/configs.jsonl
+OUT=$O bash tools/gpu_configs.sh || exit 3
 python -c "
 import json
 for l in open('$O/configs.jsonl'):

@@ -11,6 +11,6 @@ mkdir -p $O
 for n in 4 8; do
   GS_BENCH_BACKEND=gloo GS_BENCH_SHARE_GPU=1 timeout -k 10 500 python -m torch.distributed.run --nnodes=1 \
     --nproc-per-node $n --master-addr 127.0.0.1 --master-port $((29600 + n)) bench.py --gpus $n --steps 2 \
-    --warmup 1 --no-cpu-baseline > $O/weak$n.json 2> $O/weak$n.err || { tail -20 $O/weak$n.err; exit 1; }
+    --warmup 1 --full --no-cpu-baseline > $O/weak$n.json 2> $O/weak$n.err || { tail -20 $O/weak$n.err; exit 1; }
   python -c "import json; d = json.loads(open('$O/weak$n.json').read().strip().splitlines()[-1]); print('weak', $n, d['n_gpus'], d['value'], d['ms_per_step'], d['config']['parallelism'], d.get('split_step', {}) and d['split_step'].get('cams_per_rank'))"
 done

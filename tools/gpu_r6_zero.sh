@@ -12,7 +12,7 @@ tail -1 $O/tests.log
 for rep in 1 2 3; do
   for z in 1 0; do
     for c in 27 4; do
-      GS_FORWARD_ZERO_SCRATCH=$z timeout -k 10 300 python bench.py --no-cpu-baseline --cams $c > $O/b_z${z}_c${c}_$rep.json 2> $O/b_z${z}_c${c}_$rep.err || { tail $O/b_z${z}_c${c}_$rep.err; exit 3; }
+      GS_FORWARD_ZERO_SCRATCH=$z timeout -k 10 300 python bench.py --full --no-cpu-baseline --cams $c > $O/b_z${z}_c${c}_$rep.json 2> $O/b_z${z}_c${c}_$rep.err || { tail $O/b_z${z}_c${c}_$rep.err; exit 3; }
       python -c "import json; d=json.load(open('$O/b_z${z}_c${c}_$rep.json')); print('bench z=$z c=$c', d['value'], d['ms_per_step'], round(d['stages_ms_per_step']['render_fwd'],3), round(d['stages_ms_per_step']['render_bwd'],3))"
     done
   done
