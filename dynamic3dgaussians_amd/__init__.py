@@ -10,9 +10,11 @@ Layout:
   camera.py       helpers.setup_camera restatement + synthetic camera rig
   scene.py        synthetic scenes for tests and the benchmark
   distributed.py  camera-sharded data parallelism with one RCCL all-reduce
+  image_loss.py   the reference's L1 + SSIM photometric loss, fused (include/gs_loss.h)
 """
 from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, GradientSink,  # noqa: F401
                          _RasterizeGaussians, rasterize_gaussians)
 from ._C import set_default_compat, get_default_compat  # noqa: F401
+from .image_loss import photometric_image_loss, photometric_loss, photometric_loss_torch  # noqa: F401
 
 __version__ = "0.1.0"

@@ -52,6 +52,14 @@ class GsNeighborGraph(ctypes.Structure):
                 ("prev_inv_rot", c_void_p), ("rev_ptr", c_void_p), ("rev_pos", c_void_p)]
 
 
+class GsPhotoLoss(ctypes.Structure):
+    """include/gs_loss.h gs_photo_loss."""
+    _fields_ = [("B", c_int32), ("Ch", c_int32), ("H", c_int32), ("W", c_int32), ("image", c_void_p),
+                ("target", c_void_p), ("mask", c_void_p), ("gain", c_void_p), ("offset", c_void_p),
+                ("mask_batch_stride", c_int64), ("l1_weight", c_float), ("ssim_weight", c_float),
+                ("losses", c_void_p), ("workspace", c_void_p), ("workspace_bytes", ctypes.c_uint64)]
+
+
 GS_ADAM_MAX_TENSORS = 16  # include/gs_optim.h
 
 
@@ -147,6 +155,14 @@ PROTOTYPES = {
     "gs_neighbor_reverse_workspace_bytes": (c_size_t, [c_int64, c_int32]),
     "gs_neighbor_reverse": (ctypes.c_int, [c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
                                            c_void_p, c_void_p]),
+    # include/gs_loss.h
+    "gs_photo_loss_struct_bytes": (c_size_t, []),
+    "gs_photo_loss_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
+    "gs_photo_loss_validate": (ctypes.c_int, [ctypes.POINTER(GsPhotoLoss), ctypes.c_int, c_void_p, c_void_p,
+                                              c_void_p, c_void_p]),
+    "gs_photo_loss_forward": (ctypes.c_int, [ctypes.POINTER(GsPhotoLoss), c_void_p]),
+    "gs_photo_loss_backward": (ctypes.c_int, [ctypes.POINTER(GsPhotoLoss), c_void_p, c_void_p, c_void_p,
+                                              c_void_p, c_void_p]),
     "gs_timing_select": (ctypes.c_int, [ctypes.c_uint32]),
     "gs_timing_read": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(c_int64),
                                       ctypes.c_int]),

@@ -59,8 +59,10 @@ SOURCES = {
     "gs_neighbor.hip": [],
     "gs_optim.hip": ["-ffp-contract=off"],
     "gs_knn.hip": ["-ffp-contract=off"],
+    "gs_loss.hip": [],
     "gs_api.hip": [],
     "gs_host.cpp": [],  # host-only C++ (also built by oracle/Makefile's sanitizer target)
+    "gs_loss_host.cpp": [],  # host-only C++ (also built into tools/loss_host_sanitize.c's program)
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall",
           "-Wno-unused-function", "-I", CSRC, "-I", INCLUDE]

@@ -23,9 +23,13 @@ computed identically on every rank and enter with weight 1/N so the SUM
 counts them once.
 
 The default image loss is the L1 term of the reference's photometric loss
-(train.py:187, `l1_loss_v1` helpers.py:110-111); SSIM, masks, per-camera colour correction and
-the neighbour losses (neighbor.neighbor_losses) are the caller's to pass as
-`image_loss` / `extra_loss` -- they are not on the rasterizer path.
+(train.py:187, `l1_loss_v1` helpers.py:110-111).  The reference's full
+photometric loss -- 0.8 L1 + 0.2 (1 - SSIM) with masks and the per-camera
+colour correction (train.py:161-183) -- is image_loss.photometric_image_loss,
+one fused HIP forward and backward for the rank's cameras:
+`image_loss=functools.partial(photometric_image_loss, cam_m=..., cam_c=...,
+cam_ids=...)`.  The neighbour losses (neighbor.neighbor_losses) are the
+caller's to pass as `extra_loss` -- they are not on the rasterizer path.
 Densification at timestep 0 (external.py:215-292) is likewise the caller's
 `densify` callback: it replaces tensors (variables[...] and the optimizer's
 Parameters), after which the driver builds a new bucket.
