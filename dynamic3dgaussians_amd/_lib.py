@@ -60,6 +60,34 @@ class GsPhotoLoss(ctypes.Structure):
                 ("losses", c_void_p), ("workspace", c_void_p), ("workspace_bytes", ctypes.c_uint64)]
 
 
+GS_DENSIFY_MAX_TENSORS = 16  # include/gs_densify.h
+GS_DENSIFY_N_SPLIT = 2
+GS_DENSIFY_ROLES = {"plain": 0, "means": 1, "log_scales": 2, "rotations": 3, "logit_opacities": 4}
+GS_DENSIFY_CLONE, GS_DENSIFY_SPLIT, GS_DENSIFY_PRUNE, GS_DENSIFY_PRUNE_SPLIT = 1, 2, 4, 8  # the flag byte
+
+
+class GsDensifyPlanArgs(ctypes.Structure):
+    """include/gs_densify.h gs_densify_plan_args."""
+    _fields_ = [("P", c_int64), ("grad_accum", c_void_p), ("denom", c_void_p), ("log_scales", c_void_p),
+                ("logit_opacities", c_void_p), ("grad_thresh", c_float), ("clone_max_scale", c_float),
+                ("prune_min_opacity", c_float), ("prune_max_scale", c_float), ("n_split", c_int32),
+                ("_pad", c_int32), ("workspace", c_void_p), ("workspace_bytes", ctypes.c_uint64)]
+
+
+class GsDensifyTensor(ctypes.Structure):
+    """include/gs_densify.h gs_densify_tensor."""
+    _fields_ = [("src", c_void_p), ("src_exp_avg", c_void_p), ("src_exp_avg_sq", c_void_p), ("dst", c_void_p),
+                ("dst_exp_avg", c_void_p), ("dst_exp_avg_sq", c_void_p), ("width", c_int32), ("role", c_int32)]
+
+
+class GsDensifyApplyArgs(ctypes.Structure):
+    """include/gs_densify.h gs_densify_apply_args."""
+    _fields_ = [("P", c_int64), ("counts", c_int64 * 4), ("workspace", c_void_p),
+                ("workspace_bytes", ctypes.c_uint64), ("n_split", c_int32), ("n_tensors", c_int32),
+                ("noise", c_void_p), ("stats", c_void_p * 3), ("reset_opacity", c_int32),
+                ("opacity_reset", c_float), ("t", GsDensifyTensor * GS_DENSIFY_MAX_TENSORS)]
+
+
 GS_ADAM_MAX_TENSORS = 16  # include/gs_optim.h
 
 
@@ -163,6 +191,21 @@ PROTOTYPES = {
     "gs_photo_loss_forward": (ctypes.c_int, [ctypes.POINTER(GsPhotoLoss), c_void_p]),
     "gs_photo_loss_backward": (ctypes.c_int, [ctypes.POINTER(GsPhotoLoss), c_void_p, c_void_p, c_void_p,
                                               c_void_p, c_void_p]),
+    # include/gs_densify.h
+    "gs_densify_plan_struct_bytes": (c_size_t, []),
+    "gs_densify_tensor_struct_bytes": (c_size_t, []),
+    "gs_densify_apply_struct_bytes": (c_size_t, []),
+    "gs_densify_workspace_bytes": (c_size_t, [c_int64]),
+    "gs_densify_counts_offset": (c_size_t, [c_int64]),
+    "gs_densify_flags_offset": (c_size_t, [c_int64]),
+    "gs_densify_ranks_offset": (c_size_t, [c_int64]),
+    "gs_densify_scan_block": (c_int64, []),
+    "gs_densify_scan_tile": (c_int64, []),
+    "gs_densify_new_count": (c_int64, [ctypes.POINTER(c_int64), c_int32]),
+    "gs_densify_plan_validate": (ctypes.c_int, [ctypes.POINTER(GsDensifyPlanArgs)]),
+    "gs_densify_apply_validate": (ctypes.c_int, [ctypes.POINTER(GsDensifyApplyArgs)]),
+    "gs_densify_plan": (ctypes.c_int, [ctypes.POINTER(GsDensifyPlanArgs), c_void_p]),
+    "gs_densify_apply": (ctypes.c_int, [ctypes.POINTER(GsDensifyApplyArgs), c_void_p]),
     "gs_timing_select": (ctypes.c_int, [ctypes.c_uint32]),
     "gs_timing_read": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(c_int64),
                                       ctypes.c_int]),

@@ -60,8 +60,10 @@ SOURCES = {
     "gs_optim.hip": ["-ffp-contract=off"],
     "gs_knn.hip": ["-ffp-contract=off"],
     "gs_loss.hip": [],
+    "gs_densify.hip": ["-ffp-contract=off"],
     "gs_api.hip": [],
     "gs_host.cpp": [],  # host-only C++ (also built by oracle/Makefile's sanitizer target)
+    "gs_densify_host.cpp": [],  # host-only C++ (also built into tools/densify_host_sanitize.c's program)
     "gs_loss_host.cpp": [],  # host-only C++ (also built into tools/loss_host_sanitize.c's program)
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall",

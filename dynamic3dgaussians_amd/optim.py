@@ -20,7 +20,8 @@ fuses it into the same launch:
     optimizer.zero_grad(set_to_none=True)
 
 (call `densify_stats` + `densify` + `step()` separately on the iterations
-where densify() clones / splits / prunes, as the reference orders them).
+where densify() clones / splits / prunes, as the reference orders them;
+densify.py has that pass on HIP).
 No CPU path: parameters must be contiguous fp32 device tensors.
 """
 from __future__ import annotations

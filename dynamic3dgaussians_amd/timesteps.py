@@ -32,7 +32,9 @@ cam_ids=...)`.  The neighbour losses (neighbor.neighbor_losses) are the
 caller's to pass as `extra_loss` -- they are not on the rasterizer path.
 Densification at timestep 0 (external.py:215-292) is likewise the caller's
 `densify` callback: it replaces tensors (variables[...] and the optimizer's
-Parameters), after which the driver builds a new bucket.
+Parameters), after which the driver builds a new bucket.  The callback to
+pass is `functools.partial(densify.densify, accumulate=False)`, the HIP pass
+of densify.py (the driver has accumulated the statistics already).
 """
 from __future__ import annotations
 
@@ -209,7 +211,8 @@ class TimestepDriver:
         back into `optimizer`.  Densification (external.py:215-292, timestep
         0 only, train.py:436) does state surgery on the reference optimizer:
         the steps of timestep 0 take the plain path when a `densify` callback
-        is given.
+        is given; pass `functools.partial(densify, accumulate=False)` with
+        `densify` from densify.py (the statistics are accumulated here).
     `sharded` may also be a factory(params, lr, rank, world, group) ->
     ShardedStep (e.g. with a substituted update for CPU tests).
 

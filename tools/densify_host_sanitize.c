@@ -1,0 +1,140 @@
+/* densify_host_sanitize.c -- stand-alone driver of densification's host
+ * validators (dynamic3dgaussians_amd/csrc/gs_densify_host.cpp) for a CPU
+ * sanitizer build (tests/test_densify.py compiles this file, gs_host.cpp and
+ * gs_densify_host.cpp with -fsanitize=address,undefined and runs the program).
+ * It walks valid and invalid argument blocks; the validators must accept /
+ * refuse each one with a message and touch nothing they were not given.  The
+ * pointers name heap buffers of the right size, none of which a validator may
+ * dereference.  Exit status 0 and "densify host sanitize ok" on success. */
+#include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "gs_densify.h"
+
+static int failures = 0;
+
+static void expect(int ok, const char *what) {
+  if (!ok) {
+    fprintf(stderr, "FAIL: %s (last error: %s)\n", what, gs_last_error());
+    ++failures;
+  }
+}
+
+static int plan_refused(const gs_densify_plan_args *a, const char *needle) {
+  return gs_densify_plan_validate(a) < 0 && strstr(gs_last_error(), needle) != NULL;
+}
+
+static int apply_refused(const gs_densify_apply_args *a, const char *needle) {
+  return gs_densify_apply_validate(a) < 0 && strstr(gs_last_error(), needle) != NULL;
+}
+
+int main(void) {
+  const int64_t P = 3000, P_new = 4000;
+  const size_t ws_bytes = gs_densify_workspace_bytes(P);
+  expect(ws_bytes >= (size_t)P * 17 + 32, "workspace holds flags, ranks and totals");
+  expect(gs_densify_workspace_bytes(0) == 0 && gs_densify_workspace_bytes(-7) == 0, "workspace of no Gaussians is 0");
+  expect(gs_densify_plan_struct_bytes() == sizeof(gs_densify_plan_args), "plan struct size");
+  expect(gs_densify_tensor_struct_bytes() == sizeof(gs_densify_tensor), "tensor struct size");
+  expect(gs_densify_apply_struct_bytes() == sizeof(gs_densify_apply_args), "apply struct size");
+  expect(gs_densify_flags_offset(P) + (size_t)P <= gs_densify_ranks_offset(P), "flags before ranks");
+  expect(gs_densify_ranks_offset(P) + 16 * (size_t)P <= ws_bytes, "ranks inside the workspace");
+  expect(gs_densify_scan_block() > 0 && gs_densify_scan_tile() > 0, "scan geometry");
+
+  float *accum = malloc(P * sizeof(float)), *denom = malloc(P * sizeof(float));
+  float *src = malloc((size_t)P * 4 * sizeof(float)), *dst = malloc((size_t)P_new * 4 * sizeof(float));
+  float *mom = malloc((size_t)P * 4 * sizeof(float)), *dmom = malloc((size_t)P_new * 4 * sizeof(float));
+  float *noise = malloc((size_t)2 * P * 3 * sizeof(float)), *stat = malloc((size_t)P_new * sizeof(float));
+  void *ws = aligned_alloc(256, (ws_bytes + 255) / 256 * 256);
+  if (!accum || !denom || !src || !dst || !mom || !dmom || !noise || !stat || !ws) return 2;
+
+  gs_densify_plan_args plan;
+  memset(&plan, 0, sizeof(plan));
+  plan.P = P;
+  plan.grad_accum = accum; plan.denom = denom; plan.log_scales = src; plan.logit_opacities = src;
+  plan.grad_thresh = 0.0002f; plan.clone_max_scale = 0.02f; plan.prune_min_opacity = 0.005f;
+  plan.prune_max_scale = 0.0f; plan.n_split = GS_DENSIFY_N_SPLIT;
+  plan.workspace = ws; plan.workspace_bytes = ws_bytes;
+  expect(gs_densify_plan_validate(&plan) == 0, "good plan block");
+  gs_densify_plan_args empty = plan;
+  empty.P = 0; empty.grad_accum = NULL; empty.workspace = NULL; empty.workspace_bytes = 0;
+  expect(gs_densify_plan_validate(&empty) == 0, "plan of no Gaussians");
+
+  gs_densify_plan_args bp;
+  expect(plan_refused(NULL, "null argument block"), "null plan block");
+  bp = plan; bp.P = -1;               expect(plan_refused(&bp, "P must be"), "P < 0");
+  bp = plan; bp.n_split = 3;          expect(plan_refused(&bp, "n_split"), "n_split = 3");
+  bp = plan; bp.grad_thresh = NAN;    expect(plan_refused(&bp, "finite"), "NaN threshold");
+  bp = plan; bp.prune_max_scale = INFINITY; expect(plan_refused(&bp, "finite"), "infinite big-point scale");
+  bp = plan; bp.denom = NULL;         expect(plan_refused(&bp, "required"), "null denom");
+  bp = plan; bp.log_scales = (const float *)((const char *)src + 2);
+  expect(plan_refused(&bp, "4-byte aligned"), "misaligned log_scales");
+  bp = plan; bp.workspace = NULL;     expect(plan_refused(&bp, "workspace is required"), "null workspace");
+  bp = plan; bp.workspace_bytes = ws_bytes - 1; expect(plan_refused(&bp, "needed"), "short workspace");
+  bp = plan; bp.workspace = (char *)ws + 8; expect(plan_refused(&bp, "16-byte aligned"), "misaligned workspace");
+
+  gs_densify_apply_args good;
+  memset(&good, 0, sizeof(good));
+  good.P = P;
+  good.counts[GS_DENSIFY_KEPT_ORIGINALS] = 2000; good.counts[GS_DENSIFY_KEPT_CLONES] = 1000;
+  good.counts[GS_DENSIFY_ALL_SPLITS] = 600; good.counts[GS_DENSIFY_KEPT_SPLITS] = 500;
+  expect(gs_densify_new_count(good.counts, GS_DENSIFY_N_SPLIT) == P_new, "new count");
+  good.workspace = ws; good.workspace_bytes = ws_bytes;
+  good.n_split = GS_DENSIFY_N_SPLIT;
+  good.noise = noise;
+  good.stats[0] = stat; good.stats[1] = stat; good.stats[2] = stat;
+  good.opacity_reset = -4.59512f;
+  const int roles[5] = {GS_DENSIFY_ROLE_MEANS, GS_DENSIFY_ROLE_LOG_SCALES, GS_DENSIFY_ROLE_ROTATIONS,
+                        GS_DENSIFY_ROLE_LOGIT_OPACITIES, GS_DENSIFY_ROLE_PLAIN};
+  const int widths[5] = {3, 3, 4, 1, 4};
+  good.n_tensors = 5;
+  for (int t = 0; t < 5; ++t) {
+    good.t[t].src = src; good.t[t].dst = dst;
+    good.t[t].src_exp_avg = mom; good.t[t].src_exp_avg_sq = mom;
+    good.t[t].dst_exp_avg = dmom; good.t[t].dst_exp_avg_sq = dmom;
+    good.t[t].width = widths[t]; good.t[t].role = roles[t];
+  }
+  expect(gs_densify_apply_validate(&good) == 0, "good apply block");
+  gs_densify_apply_args lazy = good;  /* a tensor whose state does not exist yet */
+  lazy.t[4].src_exp_avg = lazy.t[4].src_exp_avg_sq = NULL;
+  expect(gs_densify_apply_validate(&lazy) == 0, "no source moments");
+  lazy.t[4].dst_exp_avg = lazy.t[4].dst_exp_avg_sq = NULL;
+  expect(gs_densify_apply_validate(&lazy) == 0, "no moments at all");
+
+  gs_densify_apply_args bad;
+  expect(apply_refused(NULL, "null argument block"), "null apply block");
+  bad = good; bad.P = -5;            expect(apply_refused(&bad, "P must be"), "apply P < 0");
+  bad = good; bad.n_split = 1;       expect(apply_refused(&bad, "n_split"), "apply n_split");
+  bad = good; bad.n_tensors = 17;    expect(apply_refused(&bad, "n_tensors"), "17 tensors");
+  bad = good; bad.counts[GS_DENSIFY_KEPT_SPLITS] = 700; expect(apply_refused(&bad, "counts"), "kept > all splits");
+  bad = good; bad.counts[GS_DENSIFY_KEPT_ORIGINALS] = -1; expect(apply_refused(&bad, "counts"), "negative count");
+  bad = good; bad.counts[GS_DENSIFY_KEPT_ORIGINALS] = P; expect(apply_refused(&bad, "counts"), "counts beyond P");
+  bad = good; bad.t[2].width = 0;    expect(apply_refused(&bad, "width"), "width 0");
+  bad = good; bad.t[4].width = -3;   expect(apply_refused(&bad, "width"), "width < 0");
+  bad = good; bad.t[1].width = 4;    expect(apply_refused(&bad, "has width"), "role with the wrong width");
+  bad = good; bad.t[4].role = 9;     expect(apply_refused(&bad, "unknown role"), "unknown role");
+  bad = good; bad.t[4].role = GS_DENSIFY_ROLE_MEANS; bad.t[4].width = 3;
+  expect(apply_refused(&bad, "used twice"), "role used twice");
+  bad = good; bad.t[3].role = GS_DENSIFY_ROLE_PLAIN; expect(apply_refused(&bad, "is missing"), "role missing");
+  bad = good; bad.n_tensors = 0;     expect(apply_refused(&bad, "is missing"), "no tensors");
+  bad = good; bad.t[0].src = NULL;   expect(apply_refused(&bad, "src is required"), "null src");
+  bad = good; bad.t[0].dst = NULL;   expect(apply_refused(&bad, "dst is required"), "null dst");
+  bad = good; bad.t[4].dst = (float *)((char *)dst + 1);
+  expect(apply_refused(&bad, "4-byte aligned"), "misaligned dst");
+  bad = good; bad.t[4].src_exp_avg = (const float *)((const char *)mom + 2);
+  expect(apply_refused(&bad, "4-byte aligned"), "misaligned moment");
+  bad = good; bad.t[4].dst_exp_avg_sq = NULL; expect(apply_refused(&bad, "come together"), "one moment only");
+  bad = good; bad.noise = NULL;      expect(apply_refused(&bad, "noise is required"), "null noise");
+  bad = good; bad.stats[1] = (float *)((char *)stat + 3);
+  expect(apply_refused(&bad, "4-byte aligned"), "misaligned stats");
+  bad = good; bad.reset_opacity = 1; bad.opacity_reset = NAN;
+  expect(apply_refused(&bad, "finite"), "NaN reset value");
+  bad = good; bad.workspace = NULL;  expect(apply_refused(&bad, "workspace is required"), "apply null workspace");
+  bad = good; bad.workspace_bytes = 100; expect(apply_refused(&bad, "needed"), "apply short workspace");
+
+  free(accum); free(denom); free(src); free(dst); free(mom); free(dmom); free(noise); free(stat); free(ws);
+  if (failures) return 1;
+  printf("densify host sanitize ok\n");
+  return 0;
+}
