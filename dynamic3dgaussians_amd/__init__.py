@@ -12,6 +12,7 @@ Layout:
   distributed.py  camera-sharded data parallelism with one RCCL all-reduce
   image_loss.py   the reference's L1 + SSIM photometric loss, fused (include/gs_loss.h)
   densify.py      the reference's clone / split / prune with the Adam state (include/gs_densify.h)
+  motion.py       the reference's motion-basis warp: SE(3) basis blend, fused (include/gs_motion.h)
 """
 from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, GradientSink,  # noqa: F401
                          _RasterizeGaussians, rasterize_gaussians)
@@ -20,5 +21,7 @@ from .image_loss import photometric_image_loss, photometric_loss, photometric_lo
 # `densify` here is the function; its module (schedule, plan, classify_torch, ...) is
 # importlib.import_module('dynamic3dgaussians_amd.densify')
 from .densify import densify, densify_torch  # noqa: F401
+from .motion import (MotionBases, cont_6d_to_rmat, motion_positions, motion_positions_torch,  # noqa: F401
+                     motion_transforms)
 
 __version__ = "0.1.0"

@@ -88,6 +88,16 @@ class GsDensifyApplyArgs(ctypes.Structure):
                 ("opacity_reset", c_float), ("t", GsDensifyTensor * GS_DENSIFY_MAX_TENSORS)]
 
 
+GS_MOTION_MAX_K, GS_MOTION_MAX_B = 64, 32  # include/gs_motion.h
+
+
+class GsMotionDesc(ctypes.Structure):
+    """include/gs_motion.h gs_motion_desc."""
+    _fields_ = [("G", c_int64), ("K", c_int32), ("T", c_int32), ("B", c_int32), ("coef_mode", c_int32),
+                ("rots", c_void_p), ("transls", c_void_p), ("coefs", c_void_p), ("means", c_void_p),
+                ("ts", c_int32 * GS_MOTION_MAX_B)]
+
+
 GS_ADAM_MAX_TENSORS = 16  # include/gs_optim.h
 
 
@@ -206,6 +216,16 @@ PROTOTYPES = {
     "gs_densify_apply_validate": (ctypes.c_int, [ctypes.POINTER(GsDensifyApplyArgs)]),
     "gs_densify_plan": (ctypes.c_int, [ctypes.POINTER(GsDensifyPlanArgs), c_void_p]),
     "gs_densify_apply": (ctypes.c_int, [ctypes.POINTER(GsDensifyApplyArgs), c_void_p]),
+    # include/gs_motion.h
+    "gs_motion_struct_bytes": (c_size_t, []),
+    "gs_motion_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32, ctypes.c_int]),
+    "gs_motion_backward_block": (c_int32, [c_int32, c_int32]),
+    "gs_motion_forward_validate": (ctypes.c_int, [ctypes.POINTER(GsMotionDesc), c_void_p, c_void_p, c_void_p]),
+    "gs_motion_backward_validate": (ctypes.c_int, [ctypes.POINTER(GsMotionDesc), c_void_p, c_void_p, c_void_p,
+                                                   c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gs_motion_forward": (ctypes.c_int, [ctypes.POINTER(GsMotionDesc), c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gs_motion_backward": (ctypes.c_int, [ctypes.POINTER(GsMotionDesc), c_void_p, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_void_p, c_void_p]),
     "gs_timing_select": (ctypes.c_int, [ctypes.c_uint32]),
     "gs_timing_read": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(c_int64),
                                       ctypes.c_int]),

@@ -45,6 +45,9 @@ VARIANT_FLAGS = {"": [], "stats": ["-DGS_STATS"], "stamps": ["-DGS_STAMPS"],
                  "exp_sort_copy": [],  # the tile sort's floor: copy, no sort
                  "exp_rot_all": [],  # strip_of_block's XCD rotation at C >= 8 too
                  "exp_fwd_row0": [],  # render_fwd's feature rows from 8 cached rows (gather latency)
+                 # the motion warp's two measured alternatives: a lane per (g, b) in the
+                 # forward, store-and-sum for the basis gradients
+                 "motion_alt": ["-DGS_MOTION_FWD_PAIR", "-DGS_MOTION_STORE_SUM"],
                  "ctl": []}  # the product's flags under a variant's (ctypes) binding: the A/B control
 PATCHED = ("exp_nofeat", "exp_noacc", "exp_noatomic", "exp_fwd_nofeatst", "exp_sort_copy", "exp_rot_all", "exp_fwd_row0")
 ARCH = os.environ.get("GSPLAT_OFFLOAD_ARCH", "gfx950")
@@ -61,10 +64,12 @@ SOURCES = {
     "gs_knn.hip": ["-ffp-contract=off"],
     "gs_loss.hip": [],
     "gs_densify.hip": ["-ffp-contract=off"],
+    "gs_motion.hip": [],
     "gs_api.hip": [],
     "gs_host.cpp": [],  # host-only C++ (also built by oracle/Makefile's sanitizer target)
     "gs_densify_host.cpp": [],  # host-only C++ (also built into tools/densify_host_sanitize.c's program)
     "gs_loss_host.cpp": [],  # host-only C++ (also built into tools/loss_host_sanitize.c's program)
+    "gs_motion_host.cpp": [],  # host-only C++ (also built into tools/motion_host_sanitize.c's program)
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall",
           "-Wno-unused-function", "-I", CSRC, "-I", INCLUDE]
@@ -127,8 +132,8 @@ def build(force: bool = False, verbose: bool = False) -> str:
         src, extra = item
         obj = os.path.join(BUILD_DIR, os.path.splitext(src)[0] + ".o")
         if src.endswith(".cpp"):  # host-only translation unit
-            cmd = [cc, "-x", "c++", "-O3", "-std=c++17", "-fPIC", "-Wall", "-I", CSRC, "-I", INCLUDE, *extra,
-                   "-c", os.path.join(CSRC, src), "-o", obj]
+            cmd = [cc, "-x", "c++", "-O3", "-std=c++17", "-fPIC", "-Wall", "-I", CSRC, "-I", INCLUDE,
+                   *VARIANT_FLAGS[VARIANT], *extra, "-c", os.path.join(CSRC, src), "-o", obj]
         else:
             cmd = [cc, *COMMON, *VARIANT_FLAGS[VARIANT], *extra, "-c", os.path.join(src_dir, src), "-o", obj]
         if verbose:
