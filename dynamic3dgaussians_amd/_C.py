@@ -109,10 +109,6 @@ def _feature_width(F: int) -> int:
                            f"{_lib.SUPPORTED_F[-1]}")
 
 
-def _stream(device) -> int:
-    return torch.cuda.current_stream(device).cuda_stream
-
-
 def _compat_code(compat) -> int:
     mode = _default_compat if compat is None else compat
     if mode not in _lib.GS_COMPAT:
@@ -191,7 +187,7 @@ def rasterize_gaussians(background, means3D, colors, semantic_feature, opacity, 
                                viewmatrix, projmatrix, float(c_x), float(c_y), float(tan_fovx),
                                float(tan_fovy), int(image_height), int(image_width), _opt(sh), int(degree),
                                campos, bool(prefiltered), bool(debug), cm,
-                               torch.cuda.current_stream(means3D.device).cuda_stream)
+                               _lib.stream(means3D.device))
         except RuntimeError as ex:
             raise _lib.GsplatError(str(ex)) from None
     inp = _Inputs(means3D, colors, semantic_feature, opacity, scales, rotations, scale_modifier,
@@ -217,7 +213,7 @@ def rasterize_gaussians(background, means3D, colors, semantic_feature, opacity, 
     radii = torch.empty(P, dtype=torch.int32, device=dev)
     geom = torch.empty(L_.gs_geom_buffer_bytes(P), **u8)
     img = torch.empty(L_.gs_image_buffer_bytes(W, H), **u8)
-    stream = _stream(dev)
+    stream = _lib.stream(dev)
     L = ctypes.c_int64(0)
     NI = ctypes.c_int64(0)
     check(L_.gs_forward_plan(ctypes.byref(g), ctypes.byref(cam), int(bool(prefiltered)),
@@ -254,7 +250,7 @@ def spatial_order(means3D: torch.Tensor) -> torch.Tensor:
     P = m.size(0)
     order = torch.empty(P, dtype=torch.int32, device=m.device)
     scratch = torch.empty(max(1, L_.gs_spatial_order_scratch_bytes(P)), dtype=torch.uint8, device=m.device)
-    check(L_.gs_spatial_order(P, m.data_ptr(), order.data_ptr(), scratch.data_ptr(), _stream(m.device)),
+    check(L_.gs_spatial_order(P, m.data_ptr(), order.data_ptr(), scratch.data_ptr(), _lib.stream(m.device)),
           "spatial order")
     return order
 
@@ -336,7 +332,7 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, semantic_fe
                                 geomBuffer, int(R), _opt(binningBuffer), imageBuffer, alphas, bool(debug), cm,
                                 _opt(grad_mask), None if out is None else [out[k] for k in _BUFFER_ORDER],
                                 bool(accumulate), None if densify is None else list(densify),
-                                torch.cuda.current_stream(means3D.device).cuda_stream)
+                                _lib.stream(means3D.device))
         except RuntimeError as ex:
             raise _lib.GsplatError(str(ex)) from None
     inp = _Inputs(means3D, colors, semantic_feature, None, scales, rotations, scale_modifier,
@@ -387,7 +383,7 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, semantic_fe
                 raise RuntimeError(f"densify statistics must be contiguous fp32 ({P},) tensors on {dev}")
         g.densify_accum, g.densify_denom, g.max_radius = (t.data_ptr() for t in densify)
     scratch = torch.empty(L_.gs_backward_scratch_bytes(P, inp.F), dtype=torch.uint8, device=dev)
-    stream = _stream(dev)
+    stream = _lib.stream(dev)
     p = lambda t: t.data_ptr() if (t is not None and t.numel()) else None  # noqa: E731
     check(L_.gs_backward(ctypes.byref(g), ctypes.byref(cam), radii_c.data_ptr(), int(bool(debug)), cm,
                          geomBuffer.data_ptr(), p(binningBuffer), imageBuffer.data_ptr(), int(R),
@@ -411,7 +407,7 @@ def binned_instances(imageBuffer, image_height, image_width) -> int:
     tiles = ((W + 15) // 16) * ((H + 15) // 16)
     rg = torch.empty(max(tiles, 1), 2, dtype=torch.int32, device=imageBuffer.device)
     check(L_.gs_debug_export(0, W, H, None, None, imageBuffer.data_ptr(), 0, None, None, None, None, None,
-                             None, rg.data_ptr(), None, _stream(imageBuffer.device)), "binned_instances")
+                             None, rg.data_ptr(), None, _lib.stream(imageBuffer.device)), "binned_instances")
     r = rg[:tiles].cpu().numpy().view("uint32")
     return int(r[:, 1].max()) if tiles else 0
 
@@ -429,7 +425,7 @@ def mark_visible(means3D, viewmatrix, projmatrix):
         v = _dev(viewmatrix, dev, "viewmatrix").reshape(-1)
         pr = _dev(projmatrix, dev, "projmatrix").reshape(-1)
         check(L_.gs_mark_visible(P, m.data_ptr(), v.data_ptr(), pr.data_ptr(), present.data_ptr(),
-                                 _stream(dev)), "mark_visible")
+                                 _lib.stream(dev)), "mark_visible")
     return present
 
 
@@ -576,7 +572,7 @@ def rasterize_gaussians_batch(background, means3D, colors, semantic_feature, opa
                                     bool(debug), cm, bool(activate), _windows_arg(windows, C_),
                                     _event_handle(feature_ready), cap,
                                     plan_state.hint if sync_free else [], _opt(walk_order), _opt(zero_fill),
-                                    torch.cuda.current_stream(means3D.device).cuda_stream)
+                                    _lib.stream(means3D.device))
         except RuntimeError as ex:
             raise _lib.GsplatError(str(ex)) from None
         NR, color, fmap, depth, alpha, radii, geom, binning, img, NI, layout, hint, fitted = out
@@ -616,7 +612,7 @@ def rasterize_gaussians_batch(background, means3D, colors, semantic_feature, opa
     radii = torch.empty(C, P, dtype=torch.int32, device=dev)
     geom = torch.empty(L_.gs_batch_geom_buffer_bytes(P, C), **u8)
     img = torch.empty(L_.gs_batch_image_buffer_bytes(W, H, C), **u8)
-    stream = _stream(dev)
+    stream = _lib.stream(dev)
     NR = (ctypes.c_int64 * C)()
     NI = (ctypes.c_int64 * C)()
     outs = (out_color.data_ptr(), out_feature.data_ptr() if inp.F else None, out_depth.data_ptr(),
@@ -700,7 +696,7 @@ def rasterize_gaussians_batch_backward(background, means3D, radii, colors, seman
                                       _windows_arg(windows, len(c_x)),
                                       [out.get(k, _NO_DEST) for k in _buffer_shapes(0, 0, 0)] if out else [],
                                       _opt(scratch), bool(scratch_zeroed),
-                                      torch.cuda.current_stream(means3D.device).cuda_stream)
+                                      _lib.stream(means3D.device))
         except RuntimeError as ex:
             raise _lib.GsplatError(str(ex)) from None
     inp = _Inputs(means3D, colors, semantic_feature, opacity if activate else None, scales, rotations,
@@ -759,7 +755,7 @@ def rasterize_gaussians_batch_backward(background, means3D, radii, colors, seman
             raise RuntimeError(f"scratch must be a contiguous device tensor of {nscr} bytes on {dev}")
         if scratch_zeroed:
             g.flags |= _lib.GS_FLAG_SCRATCH_ZEROED
-    stream = _stream(dev)
+    stream = _lib.stream(dev)
     p = lambda t: t.data_ptr() if (t is not None and t.numel()) else None  # noqa: E731
     check(L_.gs_backward_batch(ctypes.byref(g), cams, C, radii_c.data_ptr(), int(bool(debug)), cm,
                                geomBuffer.data_ptr(), p(binningBuffer), imageBuffer.data_ptr(), NI,

@@ -10,6 +10,8 @@ import ctypes
 import os
 import threading
 
+import torch
+
 from . import build as _build
 
 _lock = threading.Lock()
@@ -288,6 +290,11 @@ def load(auto_build: bool = True):
             raise GsplatError(f"ABI version mismatch: library reports {L.gs_version()}")
         _lib = L
         return L
+
+
+def stream(device) -> int:
+    """The gs_stream_t of a call: the device's current torch stream."""
+    return torch.cuda.current_stream(device).cuda_stream
 
 
 def check(code: int, what: str):

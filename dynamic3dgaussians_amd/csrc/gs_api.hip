@@ -1,5 +1,6 @@
-// gs_api.hip -- the C ABI (include/gsplat_hip.h): argument checks, opaque
-// state-buffer carving, launch order and error reporting.  Host code only.
+// gs_api.hip -- the rasterizer's C ABI (include/gsplat_hip.h): argument checks,
+// opaque state-buffer carving, launch order and error reporting.  Host code
+// only.  (The auxiliary ops' entry points sit next to their kernels.)
 //
 // Launch order mirrors CudaRasterizer::Rasterizer::forward/backward
 // (DGR/cuda_rasterizer/rasterizer_impl.cu:198-467), but everything goes to
@@ -15,28 +16,16 @@
 #include <thread>
 #include <vector>
 
-#include "../../include/gs_knn.h"
-#include "../../include/gs_neighbor.h"
-#include "../../include/gs_optim.h"
 #include "../../include/gsplat_hip.h"
 #include "gs_common.h"
 #include "gs_kernels.h"
+#include "gs_launch.h"
 
 using namespace gs;
 
 namespace {
 // the thread's error message (gs_host.cpp: gs_last_error)
 #define fail gs_set_error
-
-// Post-launch check: always catch launch errors; with `debug`, also
-// synchronise and surface asynchronous faults (the reference's CHECK_CUDA
-// debug mode, CR/auxiliary.h:172-179).
-int check(const char* what, int debug, hipStream_t s) {
-  hipError_t e = hipGetLastError();
-  if (e == hipSuccess && debug) e = hipStreamSynchronize(s);
-  if (e != hipSuccess) return fail((int)e, "%s: %s", what, hipGetErrorString(e));
-  return 0;
-}
 
 int higher_msb(uint32_t n) {  // getHigherMsb, CR/rasterizer_impl.cu:35-50
   uint32_t msb = sizeof(n) * 4, step = msb;
@@ -47,11 +36,6 @@ int higher_msb(uint32_t n) {  // getHigherMsb, CR/rasterizer_impl.cu:35-50
   if (n >> msb) msb++;
   return (int)msb;
 }
-
-template <class T>
-T* at(void* base, size_t off) { return reinterpret_cast<T*>(static_cast<char*>(base) + off); }
-template <class T>
-const T* at(const void* base, size_t off) { return reinterpret_cast<const T*>(static_cast<const char*>(base) + off); }
 
 bool feature_supported(int F) { return F == 0 || F == 4 || F == 8 || F == 16 || F == 32 || F == 36 || F == 64; }
 
@@ -433,12 +417,12 @@ static int plan_enqueue(const gs_gaussians* g, const gs_camera* cams, int C, int
     StageTimer t(s, GS_STAGE_PREPROCESS);
     launch_preprocess_fwd(a, cb, s);
   }
-  if (int e = check("preprocess", debug, s)) return e;
+  if (int e = launch_status("preprocess", debug, s)) return e;
   {
     StageTimer t(s, GS_STAGE_SCAN);
     launch_tile_plan(ta, cb, prefiltered, hdr_dev, s);
   }
-  return check("tile plan", debug, s);
+  return launch_status("tile plan", debug, s);
 }
 
 // The host's reading of the C plan headers: the reference's counts, the list
@@ -578,13 +562,13 @@ static int render_impl(const gs_gaussians* g, const gs_camera* cams, int C, int 
       StageTimer t(s, GS_STAGE_DUPLICATE);
       launch_tile_bucket(ta, cb, s);
     }
-    if (int e = check("duplicateWithKeys", debug, s)) return e;
+    if (int e = launch_status("duplicateWithKeys", debug, s)) return e;
     {
       StageTimer t(s, GS_STAGE_SORT);
       launch_tile_sort(ta, cb, sp.max_len, sp.total >= 0 ? sp.total : total,
                        sp.max_len >= 0 ? sp.sc : SortClasses{}, s);
     }
-    if (int e = check("tile sort", debug, s)) return e;
+    if (int e = launch_status("tile sort", debug, s)) return e;
     if (debug)
       if (int e = debug_check_lists(ta, cb, binning, L, P, (int64_t)gx * gy, sp.max_len, s))
         return e;
@@ -626,7 +610,7 @@ static int render_impl(const gs_gaussians* g, const gs_camera* cams, int C, int 
     if (mf) launch_feature_absmax(g->semantic_feature, g->P, g->F, at<uint32_t>(image, il.fmax), s);
     if (!launch_render_fwd(ra, cb, s)) return fail(-1, "unsupported feature width %d", g->F);
   }
-  return check("render", debug, s);
+  return launch_status("render", debug, s);
 }
 
 static int backward_impl(const gs_gaussians* g, const gs_camera* cams, int C, const int32_t* radii, int debug,
@@ -688,7 +672,7 @@ static int backward_impl(const gs_gaussians* g, const gs_camera* cams, int C, co
     if (!launch_render_bwd(ra, cb, s)) return fail(-1, "unsupported feature width %d", g->F);
     if (dsem_pad) launch_feature_grad_rows(dsem_pad, dL_dsemantic, P, g->F, accumulate ? 1 : 0, s);
   }
-  if (int e = check("render backward", debug, s)) return e;
+  if (int e = launch_status("render backward", debug, s)) return e;
   PreprocessBwdArgs b{};
   b.P = P; b.D = g->D; b.M = g->M; b.F = g->F; b.W = W; b.H = H; b.compat = compat;
   b.accumulate = accumulate ? 1 : 0;
@@ -710,7 +694,7 @@ static int backward_impl(const gs_gaussians* g, const gs_camera* cams, int C, co
     StageTimer t(s, GS_STAGE_PREPROCESS_BWD);
     launch_preprocess_bwd(b, cb, s);
   }
-  return check("preprocess backward", debug, s);
+  return launch_status("preprocess backward", debug, s);
 }
 
 // The sort extents of the last plan of this thread when the render belongs
@@ -908,7 +892,7 @@ int gs_mark_visible(int64_t P, const float* means3D, const float* viewmatrix, co
   if (!means3D || !viewmatrix || !present) return fail(-1, "null argument");
   hipStream_t s = (hipStream_t)stream;
   launch_mark_visible((int)P, means3D, viewmatrix, present, s);
-  return check("markVisible", 0, s);
+  return launch_status("markVisible", 0, s);
 }
 
 int gs_debug_export(int64_t P, int32_t W, int32_t H, const void* geom, const void* binning, const void* image,
@@ -946,178 +930,10 @@ int gs_debug_export(int64_t P, int32_t W, int32_t H, const void* geom, const voi
   return 0;
 }
 
-size_t gs_sort_scratch_bytes(int64_t n) { return SortLayout(n > 0 ? n : 0).total; }
-
-int gs_sort_pairs(int64_t n, uint64_t* keys, uint32_t* vals, int end_bit, void* scratch, gs_stream_t stream) {
-  if (n < 0 || end_bit < 0 || end_bit > 64) return fail(-1, "bad sort arguments");
-  if (n <= 1) return 0;
-  hipStream_t s = (hipStream_t)stream;
-  const SortLayout sl(n);
-  uint64_t* k1 = at<uint64_t>(scratch, sl.keys1);
-  uint32_t* v1 = at<uint32_t>(scratch, sl.vals1);
-  const int which = launch_radix_sort(n, keys, vals, k1, v1, at<uint32_t>(scratch, sl.hist),
-                                      at<uint32_t>(scratch, sl.rowtot), end_bit, s);
-  if (which) {
-    (void)hipMemcpyAsync(keys, k1, 8 * n, hipMemcpyDeviceToDevice, s);
-    (void)hipMemcpyAsync(vals, v1, 4 * n, hipMemcpyDeviceToDevice, s);
-  }
-  return check("sort", 0, s);
-}
-
-// ---- the binning passes' spatial walk order (gs_gaussians.walk_order) ----
-
-size_t gs_spatial_order_scratch_bytes(int64_t P) { return SpatialLayout(P < 0 ? 0 : P).total; }
-
-int gs_spatial_order(int64_t P, const float* means3D, int32_t* order, void* scratch, gs_stream_t stream) {
-  if (P < 0 || P > 0x7FFFFFFF) return fail(-1, "spatial order: P = %lld out of range", (long long)P);
-  if (P > 0 && (!means3D || !order || !scratch)) return fail(-1, "spatial order: null pointer");
-  launch_spatial_order(P, means3D, order, scratch, (hipStream_t)stream);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : fail((int)e, "spatial order: %s", hipGetErrorString(e));
-}
-
-// ---- exact k-nearest neighbours (include/gs_knn.h) ----
-
-size_t gs_knn_workspace_bytes(int64_t N) { return KnnLayout(N < 0 ? 0 : N).total; }
-
-int gs_knn(int64_t N, int32_t K, const float* points, double* sq_dist, int64_t* index, void* workspace,
-           gs_stream_t stream) {
-  if (N < 0) return fail(-1, "N must be >= 0");
-  if (K < 1 || K > GS_KNN_MAX_K) return fail(-1, "K must be in [1, %d] (got %d)", GS_KNN_MAX_K, K);
-  if (N >= (int64_t)1 << 31) return fail(-1, "N must fit in int32");
-  if (N == 0) return 0;
-  if (!points || !sq_dist || !index || !workspace) return fail(-1, "knn: null argument");
-  hipStream_t s = (hipStream_t)stream;
-  if (!launch_knn(N, K, points, sq_dist, index, workspace, s)) return fail(-1, "knn: unsupported K %d", K);
-  return check("knn", 0, s);
-}
-
-// ---- fused Adam + densification statistics (include/gs_optim.h) ----
-
-int gs_adam_step(const gs_adam_args* a, const gs_densify_stats* st, gs_stream_t stream) {
-  if (!a) return fail(-1, "null Adam arguments");
-  if (a->n_tensors < 0 || a->n_tensors > GS_ADAM_MAX_TENSORS)
-    return fail(-1, "n_tensors must be in [0, %d] (got %d)", GS_ADAM_MAX_TENSORS, a->n_tensors);
-  for (int t = 0; t < a->n_tensors; ++t) {
-    const gs_adam_tensor& x = a->t[t];
-    if (x.numel < 0) return fail(-1, "tensor %d: numel < 0", t);
-    if (x.numel > 0 && (!x.param || !x.grad || !x.exp_avg || !x.exp_avg_sq))
-      return fail(-1, "tensor %d: param, grad, exp_avg and exp_avg_sq are required", t);
-    if (!(x.bc2_sqrt > 0.f)) return fail(-1, "tensor %d: bc2_sqrt must be > 0 (step >= 1)", t);
-  }
-  if (st && st->P > 0) {
-    if (!st->radii) return fail(-1, "densify stats: radii are required");
-    if (st->grad_accum && (!st->denom || !st->means2D_grad))
-      return fail(-1, "densify stats: grad_accum needs denom and means2D_grad");
-  }
-  hipStream_t s = (hipStream_t)stream;
-  if (!launch_adam_step(*a, st, s)) return fail(-1, "Adam step: too many blocks");
-  return check("adam step", 0, s);
-}
-
-// ---- neighbour losses (include/gs_neighbor.h) ----
-
-static int check_graph(const gs_neighbor_graph* g, bool backward, NeighborArgs* a) {
-  if (!g) return fail(-1, "null neighbour graph");
-  if (g->N < 0 || g->K < 0) return fail(-1, "N and K must be >= 0 (got N=%lld K=%d)", (long long)g->N, g->K);
-  if ((double)g->N * g->K >= 2147483647.0) return fail(-1, "N*K must fit in int32 (got N=%lld K=%d)", (long long)g->N, g->K);
-  if (g->N > 0 && (!g->prev_inv_rot || (g->K > 0 && (!g->nbr || !g->weight || !g->dist || !g->prev_offset))))
-    return fail(-1, "neighbour graph arrays are required");
-  if (backward && g->N > 0 && (!g->rev_ptr || (g->K > 0 && !g->rev_pos)))
-    return fail(-1, "the backward needs the reverse CSR (gs_neighbor_reverse)");
-  *a = NeighborArgs{g->N, g->K, nullptr, nullptr, g->nbr, g->weight, g->dist, g->prev_offset, g->prev_inv_rot,
-                    g->rev_ptr, g->rev_pos};
-  return 0;
-}
-
-size_t gs_neighbor_workspace_bytes(int64_t N, int32_t K, int backward) {
-  return NeighborLayout(N < 0 ? 0 : N, K < 0 ? 0 : K, backward != 0).total;
-}
-
-int gs_neighbor_loss_forward(const gs_neighbor_graph* g, const float* fg_pts, const float* fg_rot, float* losses,
-                             void* workspace, gs_stream_t stream) {
-  NeighborArgs a;
-  if (int e = check_graph(g, false, &a)) return e;
-  if (!losses || !workspace) return fail(-1, "losses and workspace are required");
-  if (a.N > 0 && (!fg_pts || !fg_rot)) return fail(-1, "fg_pts and fg_rot are required");
-  a.fg_pts = fg_pts;
-  a.fg_rot = fg_rot;
-  hipStream_t s = (hipStream_t)stream;
-  launch_neighbor_forward(a, losses, workspace, s);
-  return check("neighbour loss forward", 0, s);
-}
-
-int gs_neighbor_loss_backward(const gs_neighbor_graph* g, const float* fg_pts, const float* fg_rot,
-                              const float* dL_dlosses, float* d_fg_pts, float* d_fg_rot, void* workspace,
-                              gs_stream_t stream) {
-  NeighborArgs a;
-  if (int e = check_graph(g, true, &a)) return e;
-  if (a.N == 0) return 0;
-  if (!fg_pts || !fg_rot || !dL_dlosses || !d_fg_pts || !d_fg_rot || !workspace)
-    return fail(-1, "neighbour loss backward: null argument");
-  a.fg_pts = fg_pts;
-  a.fg_rot = fg_rot;
-  hipStream_t s = (hipStream_t)stream;
-  launch_neighbor_backward(a, dL_dlosses, d_fg_pts, d_fg_rot, workspace, s);
-  return check("neighbour loss backward", 0, s);
-}
-
-namespace {
-struct RevLayout {
-  size_t keys, vals, status, sort, total;
-  explicit RevLayout(int64_t NK) {
-    size_t o = 0;
-    keys = o; o = align_up(o + 8 * (size_t)NK, 256);
-    vals = o; o = align_up(o + 4 * (size_t)NK, 256);
-    status = o; o = align_up(o + 4, 256);
-    sort = o; o = align_up(o + SortLayout(NK).total, 256);
-    total = o;
-  }
-};
-}  // namespace
-
-size_t gs_neighbor_reverse_workspace_bytes(int64_t N, int32_t K) {
-  return RevLayout((N < 0 ? 0 : N) * (K < 0 ? 0 : K)).total;
-}
-
-int gs_neighbor_reverse(int64_t N, int32_t K, const int64_t* nbr, int32_t* rev_ptr, int32_t* rev_pair,
-                        int32_t* rev_pos, void* workspace, gs_stream_t stream) {
-  if (N < 0 || K < 0) return fail(-1, "N and K must be >= 0");
-  if ((double)N * K >= 2147483647.0) return fail(-1, "N*K must fit in int32");
-  const int64_t NK = N * K;
-  if (!rev_ptr || !workspace || (NK > 0 && (!nbr || !rev_pos))) return fail(-1, "neighbour reverse: null argument");
-  hipStream_t s = (hipStream_t)stream;
-  const RevLayout L(NK);
-  uint64_t* keys = at<uint64_t>(workspace, L.keys);
-  uint32_t* vals = at<uint32_t>(workspace, L.vals);
-  int* status = at<int>(workspace, L.status);
-  (void)hipMemsetAsync(status, 0, 4, s);
-  launch_neighbor_rev_keys(NK, N, nbr, keys, vals, status, s);
-  if (NK > 1) {
-    const SortLayout sl(NK);
-    void* sc = at<char>(workspace, L.sort);
-    uint64_t* k1 = at<uint64_t>(sc, sl.keys1);
-    uint32_t* v1 = at<uint32_t>(sc, sl.vals1);
-    int end_bit = 1;  // keys <= N (N marks invalid ids)
-    while (end_bit < 63 && ((uint64_t)N >> end_bit)) ++end_bit;
-    if (launch_radix_sort(NK, keys, vals, k1, v1, at<uint32_t>(sc, sl.hist), at<uint32_t>(sc, sl.rowtot),
-                          end_bit, s)) {
-      keys = k1;
-      vals = v1;
-    }
-  }
-  launch_neighbor_rev_ptr(NK, N, keys, vals, rev_ptr, rev_pair, rev_pos, s);
-  int host_status = 0;
-  (void)hipMemcpyAsync(&host_status, status, 4, hipMemcpyDeviceToHost, s);
-  if (int e = check("neighbour reverse", 1, s)) return e;
-  if (host_status) return fail(-1, "neighbor_indices out of range [0, %lld)", (long long)N);
-  return 0;
-}
-
 int gs_test_wave_reduce(int n_comp, const float* in, float* out, gs_stream_t stream) {
   if (n_comp < 1 || n_comp > 64) return fail(-1, "n_comp must be in [1, 64]");
   launch_test_wave_reduce(n_comp, in, out, (hipStream_t)stream);
-  return check("wave reduce test", 1, (hipStream_t)stream);
+  return launch_status("wave reduce test", 1, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -4,19 +4,12 @@
 // tested, cub::DeviceRadixSort::SortPairs-compatible utility
 // (DGR/cuda_rasterizer/rasterizer_impl.cu:306-314 semantics: stable, bits
 // [0, end_bit)).  Wave64 match-by-ballot ranking keeps every pass stable.
+#include "../../include/gsplat_hip.h"
 #include "gs_common.h"
 #include "gs_kernels.h"
+#include "gs_launch.h"
 
 namespace gs {
-
-__device__ inline uint32_t wave_incl_scan(uint32_t x, int lane) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    uint32_t y = __shfl_up(x, o, 64);
-    if (lane >= o) x += y;
-  }
-  return x;
-}
 
 // Block-wide exclusive scan of one value per thread (256 threads); returns the
 // exclusive prefix and writes the block total to *total.
@@ -160,3 +153,27 @@ int launch_radix_sort(int64_t n, uint64_t* keys0, uint32_t* vals0, uint64_t* key
 }
 
 }  // namespace gs
+
+using namespace gs;
+
+extern "C" {
+
+size_t gs_sort_scratch_bytes(int64_t n) { return SortLayout(n > 0 ? n : 0).total; }
+
+int gs_sort_pairs(int64_t n, uint64_t* keys, uint32_t* vals, int end_bit, void* scratch, gs_stream_t stream) {
+  if (n < 0 || end_bit < 0 || end_bit > 64) return gs_set_error(-1, "bad sort arguments");
+  if (n <= 1) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  const SortLayout sl(n);
+  uint64_t* k1 = at<uint64_t>(scratch, sl.keys1);
+  uint32_t* v1 = at<uint32_t>(scratch, sl.vals1);
+  const int which = launch_radix_sort(n, keys, vals, k1, v1, at<uint32_t>(scratch, sl.hist),
+                                      at<uint32_t>(scratch, sl.rowtot), end_bit, s);
+  if (which) {
+    (void)hipMemcpyAsync(keys, k1, 8 * n, hipMemcpyDeviceToDevice, s);
+    (void)hipMemcpyAsync(vals, v1, 4 * n, hipMemcpyDeviceToDevice, s);
+  }
+  return launch_status("sort", 0, s);
+}
+
+}  // extern "C"

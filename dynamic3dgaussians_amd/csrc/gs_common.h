@@ -304,6 +304,26 @@ __device__ inline float wave_reduce_transposed(float (&v)[64], int lane) {
   return v[0];
 }
 
+// Inclusive scan over the wave's 64 lanes (lane = threadIdx & 63).
+template <class T>
+__device__ inline T wave_incl_scan(T x, int lane) {
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const T y = __shfl_up(x, o, 64);
+    if (lane >= o) x += y;
+  }
+  return x;
+}
+// Sum over the wave's 64 lanes, in every lane.  The order (xor 32 down to 1,
+// the running value on the left) is part of the float results of the
+// photometric and neighbour losses: keep it.
+template <class T>
+__device__ inline T wave_sum(T x) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
+  return x;
+}
+
 __device__ inline float wave_max_f(float x) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) x = fmaxf(x, __shfl_xor(x, o, 64));

@@ -27,8 +27,10 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/gs_densify.h"
+#include "gs_common.h"
 #include "gs_densify_layout.h"
-#include "gs_meta.h"
+#include "gs_host_util.h"
+#include "gs_launch.h"
 
 namespace gs {
 
@@ -71,18 +73,11 @@ __device__ inline unsigned classify(const PlanK& k, int64_t i) {
   return f;
 }
 
-__device__ inline uint64_t shfl_up64(uint64_t v, int o) { return (uint64_t)__shfl_up((long long)v, o, 64); }
-
 // Exclusive scan of one 64-bit value per thread over the workgroup's
 // DN_THREADS threads; *total = the workgroup's sum.  sh holds one word per wave.
 __device__ inline uint64_t block_excl_scan64(uint64_t x, uint64_t* sh, uint64_t* total) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  uint64_t inc = x;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint64_t y = shfl_up64(inc, o);
-    if (lane >= o) inc += y;
-  }
+  const uint64_t inc = wave_incl_scan(x, lane);
   if (lane == 63) sh[wave] = inc;
   __syncthreads();
   uint64_t before = 0, all = 0;
@@ -134,12 +129,7 @@ __global__ void __launch_bounds__(DN_THREADS) dn_scan_sums_kernel(int64_t blocks
     int excl[4], all[4];
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-      int inc = mine[c];
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const int y = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += y;
-      }
+      const int inc = wave_incl_scan(mine[c], lane);
       if (lane == 63) sh[c][wave] = inc;
       excl[c] = inc - mine[c];
     }
@@ -371,13 +361,6 @@ __global__ void __launch_bounds__(DN_THREADS) dn_apply_kernel(const ApplyK k) {
   }
 }
 
-int launched(const char* what) {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : gs_set_error((int)e, "%s: %s", what, hipGetErrorString(e));
-}
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 }  // namespace
 
 }  // namespace gs
@@ -412,7 +395,7 @@ int gs_densify_plan(const gs_densify_plan_args* args, gs_stream_t stream) {
   hipLaunchKernelGGL(dn_classify_kernel, dim3((unsigned)L.blocks), dim3(DN_THREADS), 0, s, k, flags, sums);
   hipLaunchKernelGGL(dn_scan_sums_kernel, dim3(1), dim3(DN_THREADS), 0, s, L.blocks, sums, counts);
   hipLaunchKernelGGL(dn_rank_kernel, dim3((unsigned)L.blocks), dim3(DN_THREADS), 0, s, a.P, flags, sums, ranks);
-  return launched("densify plan");
+  return launch_status("densify plan", 0, s);
 }
 
 int gs_densify_apply(const gs_densify_apply_args* args, gs_stream_t stream) {
@@ -463,7 +446,7 @@ int gs_densify_apply(const gs_densify_apply_args* args, gs_stream_t stream) {
   if (c == 0) return 0;
   if (c > 0x7FFFFFFF) return gs_set_error(-1, "densify apply: too many workgroups (%lld)", (long long)c);
   hipLaunchKernelGGL(dn_apply_kernel, dim3((unsigned)c), dim3(DN_THREADS), 0, (hipStream_t)stream, k);
-  return launched("densify apply");
+  return launch_status("densify apply", 0, (hipStream_t)stream);
 }
 
 }  // extern "C"

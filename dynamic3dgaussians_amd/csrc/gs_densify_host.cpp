@@ -9,25 +9,13 @@
 
 #include "../../include/gs_densify.h"
 #include "gs_densify_layout.h"
-#include "gs_meta.h"
+#include "gs_host_util.h"
 
 using namespace gs;
 
 namespace {
-bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
-
 const char* const ROLE_NAME[] = {"plain", "means", "log_scales", "rotations", "logit_opacities"};
 const int ROLE_WIDTH[] = {0, 3, 3, 4, 1};
-
-int check_workspace(const char* who, const void* ws, uint64_t bytes, int64_t P) {
-  const DensifyLayout L(P);
-  if (L.total == 0) return 0;
-  if (!ws) return gs_set_error(-1, "%s: workspace is required (%zu bytes)", who, L.total);
-  if (bytes < L.total)
-    return gs_set_error(-1, "%s: workspace of %llu bytes, %zu needed", who, (unsigned long long)bytes, L.total);
-  if (reinterpret_cast<uintptr_t>(ws) & 15u) return gs_set_error(-1, "%s: workspace must be 16-byte aligned", who);
-  return 0;
-}
 }  // namespace
 
 extern "C" {
@@ -63,7 +51,7 @@ int gs_densify_plan_validate(const gs_densify_plan_args* a) {
     return gs_set_error(-1, "densify plan: grad_accum, denom, log_scales and logit_opacities are required");
   if (!aligned4(a->grad_accum) || !aligned4(a->denom) || !aligned4(a->log_scales) || !aligned4(a->logit_opacities))
     return gs_set_error(-1, "densify plan: the inputs must be 4-byte aligned");
-  return check_workspace("densify plan", a->workspace, a->workspace_bytes, a->P);
+  return check_workspace("densify plan", a->workspace, a->workspace_bytes, DensifyLayout(a->P).total);
 }
 
 int gs_densify_apply_validate(const gs_densify_apply_args* a) {
@@ -111,7 +99,7 @@ int gs_densify_apply_validate(const gs_densify_apply_args* a) {
     return gs_set_error(-1, "densify apply: noise is required (%lld rows)", (long long)(a->n_split * as));
   if (!aligned4(a->noise) || !aligned4(a->stats[0]) || !aligned4(a->stats[1]) || !aligned4(a->stats[2]))
     return gs_set_error(-1, "densify apply: noise and stats must be 4-byte aligned");
-  return check_workspace("densify apply", a->workspace, a->workspace_bytes, a->P);
+  return check_workspace("densify apply", a->workspace, a->workspace_bytes, DensifyLayout(a->P).total);
 }
 
 }  // extern "C"

@@ -18,8 +18,10 @@
 
 #include <cfloat>
 
+#include "../../include/gs_knn.h"
 #include "gs_common.h"
 #include "gs_kernels.h"
+#include "gs_launch.h"
 
 namespace gs {
 
@@ -216,18 +218,19 @@ __global__ void __launch_bounds__(KB) knn_query_kernel(int64_t N, int K, int nbo
 
 inline unsigned blocks_for(int64_t n, int t) { return (unsigned)((n + t - 1) / t); }
 
-}  // namespace
-
-KnnLayout::KnnLayout(int64_t N) {
-  size_t o = 0;
-  bbox = o; o = align_up(o + 32, 256);
-  keys = o; o = align_up(o + 8 * (size_t)N, 256);
-  vals = o; o = align_up(o + 4 * (size_t)N, 256);
-  sort = o; o = align_up(o + SortLayout(N).total, 256);
-  spts = o; o = align_up(o + 16 * (size_t)N, 256);
-  boxes = o; o = align_up(o + 32 * (size_t)((N + KB - 1) / KB + 1), 256);
-  total = o;
-}
+struct KnnLayout {
+  size_t bbox, keys, vals, sort, spts, boxes, total;
+  explicit KnnLayout(int64_t N) {
+    size_t o = 0;
+    bbox = o; o = align_up(o + 32, 256);
+    keys = o; o = align_up(o + 8 * (size_t)N, 256);
+    vals = o; o = align_up(o + 4 * (size_t)N, 256);
+    sort = o; o = align_up(o + SortLayout(N).total, 256);
+    spts = o; o = align_up(o + 16 * (size_t)N, 256);
+    boxes = o; o = align_up(o + 32 * (size_t)((N + KB - 1) / KB + 1), 256);
+    total = o;
+  }
+};
 
 bool launch_knn(int64_t N, int K, const float* pts, double* out_d, int64_t* out_i, void* ws, hipStream_t s) {
   if (N <= 0 || K <= 0) return true;
@@ -270,14 +273,19 @@ bool launch_knn(int64_t N, int K, const float* pts, double* out_d, int64_t* out_
   return true;
 }
 
-SpatialLayout::SpatialLayout(int64_t N) {
-  size_t o = 0;
-  bbox = o; o = align_up(o + 32, 256);
-  keys = o; o = align_up(o + 8 * (size_t)N, 256);
-  vals = o; o = align_up(o + 4 * (size_t)N, 256);
-  sort = o; o = align_up(o + SortLayout(N).total, 256);
-  total = o;
-}
+// Spatial walk order of the binning passes (gs_spatial_order): the ids in 3-D
+// Morton order of the points (the kNN's bounding box, codes and radix sort).
+struct SpatialLayout {
+  size_t bbox, keys, vals, sort, total;
+  explicit SpatialLayout(int64_t N) {
+    size_t o = 0;
+    bbox = o; o = align_up(o + 32, 256);
+    keys = o; o = align_up(o + 8 * (size_t)N, 256);
+    vals = o; o = align_up(o + 4 * (size_t)N, 256);
+    sort = o; o = align_up(o + SortLayout(N).total, 256);
+    total = o;
+  }
+};
 
 // The binning passes' walk order: the point ids sorted by the 30-bit Morton
 // code of their position in the bounding box (the kNN's first three steps).
@@ -309,4 +317,39 @@ void launch_spatial_order(int64_t N, const float* pts, int32_t* order, void* ws,
   (void)hipMemcpyAsync(order, vals, 4 * (size_t)N, hipMemcpyDeviceToDevice, s);
 }
 
+}  // namespace
+
 }  // namespace gs
+
+using namespace gs;
+
+extern "C" {
+
+// ---- the binning passes' spatial walk order (gs_gaussians.walk_order) ----
+
+size_t gs_spatial_order_scratch_bytes(int64_t P) { return SpatialLayout(P < 0 ? 0 : P).total; }
+
+int gs_spatial_order(int64_t P, const float* means3D, int32_t* order, void* scratch, gs_stream_t stream) {
+  if (P < 0 || P > 0x7FFFFFFF) return gs_set_error(-1, "spatial order: P = %lld out of range", (long long)P);
+  if (P > 0 && (!means3D || !order || !scratch)) return gs_set_error(-1, "spatial order: null pointer");
+  launch_spatial_order(P, means3D, order, scratch, (hipStream_t)stream);
+  return launch_status("spatial order", 0, (hipStream_t)stream);
+}
+
+// ---- exact k-nearest neighbours (include/gs_knn.h) ----
+
+size_t gs_knn_workspace_bytes(int64_t N) { return KnnLayout(N < 0 ? 0 : N).total; }
+
+int gs_knn(int64_t N, int32_t K, const float* points, double* sq_dist, int64_t* index, void* workspace,
+           gs_stream_t stream) {
+  if (N < 0) return gs_set_error(-1, "N must be >= 0");
+  if (K < 1 || K > GS_KNN_MAX_K) return gs_set_error(-1, "K must be in [1, %d] (got %d)", GS_KNN_MAX_K, K);
+  if (N >= (int64_t)1 << 31) return gs_set_error(-1, "N must fit in int32");
+  if (N == 0) return 0;
+  if (!points || !sq_dist || !index || !workspace) return gs_set_error(-1, "knn: null argument");
+  hipStream_t s = (hipStream_t)stream;
+  if (!launch_knn(N, K, points, sq_dist, index, workspace, s)) return gs_set_error(-1, "knn: unsupported K %d", K);
+  return launch_status("knn", 0, s);
+}
+
+}  // extern "C"

@@ -26,8 +26,9 @@
 #include <stdint.h>
 
 #include "../../include/gs_loss.h"
+#include "gs_common.h"
+#include "gs_launch.h"
 #include "gs_loss_layout.h"
-#include "gs_meta.h"
 
 using namespace gs;
 
@@ -74,12 +75,6 @@ __device__ inline TilePos tile_pos(const PhotoArgs& a) {
 // same x, and sign(x - y) agrees with the reference at the kink of |x - y|.
 __device__ inline float corrected(float g, float v, float o, float m) {
   return __fmul_rn(__fadd_rn(__fmul_rn(g, v), o), m);
-}
-
-__device__ inline float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 
 // Workgroup sums of two values in a fixed order; thread 0 writes out[0..1].
@@ -395,11 +390,6 @@ PhotoArgs kernel_args(const gs_photo_loss& a, const PhotoLossLayout& L) {
   return k;
 }
 
-int launched(const char* what) {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : gs_set_error((int)e, "%s: %s", what, hipGetErrorString(e));
-}
-
 }  // namespace
 
 extern "C" {
@@ -417,7 +407,7 @@ int gs_photo_loss_forward(const gs_photo_loss* args, gs_stream_t stream) {
                      L.planes * L.plane_elems, pqr, partial);
   hipLaunchKernelGGL(pl_fwd_final_kernel, dim3((unsigned)a.B), dim3(PL_THREADS), 0, s, (int64_t)a.Ch * L.tiles,
                      (double)a.Ch * a.H * a.W, a.l1_weight, a.ssim_weight, partial, a.losses);
-  return launched("photometric loss forward");
+  return launch_status("photometric loss forward", 0, s);
 }
 
 int gs_photo_loss_backward(const gs_photo_loss* args, const float* dL_dloss, float* dL_dimage, float* dL_dgain,
@@ -435,7 +425,7 @@ int gs_photo_loss_backward(const gs_photo_loss* args, const float* dL_dloss, flo
   if (dL_dgain || dL_doffset)
     hipLaunchKernelGGL(pl_bwd_final_kernel, dim3((unsigned)L.planes), dim3(64), 0, s, (int)L.tiles, partial,
                        dL_dgain, dL_doffset);
-  return launched("photometric loss backward");
+  return launch_status("photometric loss backward", 0, s);
 }
 
 }  // extern "C"

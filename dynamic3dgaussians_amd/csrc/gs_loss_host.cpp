@@ -8,14 +8,10 @@
 #include <stdint.h>
 
 #include "../../include/gs_loss.h"
+#include "gs_host_util.h"
 #include "gs_loss_layout.h"
-#include "gs_meta.h"
 
 using namespace gs;
-
-namespace {
-bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
-}  // namespace
 
 extern "C" {
 
@@ -46,12 +42,7 @@ int gs_photo_loss_validate(const gs_photo_loss* a, int backward, const float* dL
                         (long long)L.plane_elems, (long long)a->mask_batch_stride);
   if (!isfinite(a->l1_weight) || !isfinite(a->ssim_weight))
     return gs_set_error(-1, "photometric loss: l1_weight and ssim_weight must be finite");
-  if (L.total > 0 && !a->workspace) return gs_set_error(-1, "photometric loss: workspace is required (%zu bytes)", L.total);
-  if (a->workspace_bytes < L.total)
-    return gs_set_error(-1, "photometric loss: workspace of %llu bytes, %zu needed",
-                        (unsigned long long)a->workspace_bytes, L.total);
-  if (reinterpret_cast<uintptr_t>(a->workspace) & 15u)
-    return gs_set_error(-1, "photometric loss: workspace must be 16-byte aligned");
+  if (int e = check_workspace("photometric loss", a->workspace, a->workspace_bytes, L.total)) return e;
   if (backward) {
     if (!dL_dloss) return gs_set_error(-1, "photometric loss backward: dL_dloss is required");
     if (!dL_dimage) return gs_set_error(-1, "photometric loss backward: dL_dimage is required");

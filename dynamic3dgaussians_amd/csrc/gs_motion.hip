@@ -31,7 +31,8 @@
 #include <stdint.h>
 
 #include "../../include/gs_motion.h"
-#include "gs_meta.h"
+#include "gs_host_util.h"
+#include "gs_launch.h"
 #include "gs_motion_layout.h"
 
 namespace gs {
@@ -466,13 +467,6 @@ __global__ void __launch_bounds__(MT_THREADS)
     d_transls[row * 3 + (j - 6)] = a;
 }
 
-int launched(const char* what) {
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : gs_set_error((int)e, "%s: %s", what, hipGetErrorString(e));
-}
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 MotionK kernel_args(const gs_motion_desc& d) {
   MotionK k{};
   k.G = d.G;
@@ -524,7 +518,7 @@ int gs_motion_forward(const gs_motion_desc* desc, float* positions, float* trans
   hipLaunchKernelGGL(mt_forward_kernel, dim3((unsigned)blocks), dim3(MT_THREADS), lds, (hipStream_t)stream,
                      kernel_args(d), positions, transforms, aligned16(transforms) ? 1 : 0);
 #endif
-  return launched("motion forward");
+  return launch_status("motion forward", 0, (hipStream_t)stream);
 }
 
 int gs_motion_backward(const gs_motion_desc* desc, const float* d_positions, const float* d_transforms,
@@ -568,7 +562,7 @@ int gs_motion_backward(const gs_motion_desc* desc, const float* d_positions, con
   }
   hipLaunchKernelGGL(mt_scatter_kernel, dim3((unsigned)scatter_blocks), dim3(MT_THREADS), 0, s, k, sum, d_rots,
                      d_transls);
-  return launched("motion backward");
+  return launch_status("motion backward", 0, s);
 }
 
 }  // extern "C"

@@ -7,7 +7,7 @@
 #include <stdint.h>
 
 #include "../../include/gs_motion.h"
-#include "gs_meta.h"
+#include "gs_host_util.h"
 #include "gs_motion_layout.h"
 
 using namespace gs;
@@ -15,8 +15,6 @@ using namespace gs;
 static_assert(GS_MOTION_MAX_K == MT_MAX_K && GS_MOTION_MAX_B == MT_MAX_B, "gs_motion.h and gs_motion_layout.h");
 
 namespace {
-bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
-
 // the descriptor alone: envelope, tables, frame indices
 int check_desc(const char* who, const gs_motion_desc* d) {
   if (!d) return gs_set_error(-1, "%s: null descriptor", who);
@@ -80,10 +78,9 @@ int gs_motion_backward_validate(const gs_motion_desc* d, const float* d_position
   if (d_positions && !d->means) return gs_set_error(-1, "%s: d_positions needs means", who);
   if (d_means && !d->means) return gs_set_error(-1, "%s: d_means needs means", who);
   if (!d_coefs) return gs_set_error(-1, "%s: d_coefs is required", who);
-  if (!workspace)
-    return gs_set_error(-1, "%s: workspace is required (%zu bytes)", who, MotionLayout(d->G, d->K, d->B).total);
-  if (reinterpret_cast<uintptr_t>(workspace) & 15u) return gs_set_error(-1, "%s: workspace must be 16-byte aligned", who);
-  return 0;
+  // the ABI carries no byte count: required and aligned only
+  const size_t need = MotionLayout(d->G, d->K, d->B).total;
+  return check_workspace(who, workspace, need, need);
 }
 
 }  // extern "C"

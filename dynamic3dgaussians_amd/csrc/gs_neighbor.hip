@@ -21,8 +21,10 @@
 // All HBM-bound (tens of bytes per pair), no matrix work.
 #include <hip/hip_runtime.h>
 
+#include "../../include/gs_neighbor.h"
 #include "gs_common.h"
 #include "gs_kernels.h"
+#include "gs_launch.h"
 
 namespace gs {
 
@@ -157,12 +159,6 @@ __device__ inline float4 rotation_bwd(const float (&G)[9], float4 q, float invn)
   const float proj = r * dr + x * dx + y * dy + z * dz;
   return make_float4((dr - r * proj) * invn, (dx - x * proj) * invn, (dy - y * proj) * invn,
                      (dz - z * proj) * invn);
-}
-
-__device__ inline float wave_sum(float x) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-  return x;
 }
 
 // Block sums of three per-lane values -> partial[block] (fixed order).
@@ -441,6 +437,35 @@ __global__ void nb_rev_ptr_kernel(int64_t NK, int64_t N, const uint64_t* __restr
 inline unsigned blocks_for(int64_t n, int t) { return (unsigned)((n + t - 1) / t); }
 inline unsigned capped(int64_t b) { return (unsigned)(b < NB_MAX_BLOCKS ? (b > 0 ? b : 1) : NB_MAX_BLOCKS); }
 
+struct NeighborArgs {
+  int64_t N;
+  int K;
+  const float* fg_pts;        // N x 3
+  const float* fg_rot;        // N x 4
+  const int64_t* nbr;         // N x K
+  const float* weight;        // N x K
+  const float* dist;          // N x K
+  const float* prev_offset;   // N x K x 3
+  const float* prev_inv_rot;  // N x 4
+  const int32_t* rev_ptr;     // N + 1
+  const int32_t* rev_pos;     // N x K: slot of pair i*K+k in the reverse order
+};
+struct NeighborLayout {
+  size_t qv, Rm, partial, revbuf, selfbuf, total;
+  NeighborLayout(int64_t N, int K, bool backward) {
+    size_t o = 0;
+    qv = o; o = align_up(o + 16 * (size_t)N, 256);
+    Rm = o; o = align_up(o + sizeof(float) * RM * (size_t)N, 256);
+    partial = o; o = align_up(o + sizeof(double) * 3 * NB_MAX_BLOCKS, 256);
+    revbuf = selfbuf = o;
+    if (backward) {
+      revbuf = o; o = align_up(o + 32 * (size_t)N * K, 256);
+      selfbuf = o; o = align_up(o + 32 * (size_t)N, 256);
+    }
+    total = o;
+  }
+};
+
 struct Work {
   float4* qv;
   float* Rm;
@@ -453,21 +478,6 @@ Work carve(const NeighborLayout& L, void* ws) {
   return Work{reinterpret_cast<float4*>(w + L.qv), reinterpret_cast<float*>(w + L.Rm),
               reinterpret_cast<double*>(w + L.partial), reinterpret_cast<float4*>(w + L.revbuf),
               reinterpret_cast<float4*>(w + L.selfbuf)};
-}
-
-}  // namespace
-
-NeighborLayout::NeighborLayout(int64_t N, int K, bool backward) {
-  size_t o = 0;
-  qv = o; o = align_up(o + 16 * (size_t)N, 256);
-  Rm = o; o = align_up(o + sizeof(float) * RM * (size_t)N, 256);
-  partial = o; o = align_up(o + sizeof(double) * 3 * NB_MAX_BLOCKS, 256);
-  revbuf = selfbuf = o;
-  if (backward) {
-    revbuf = o; o = align_up(o + 32 * (size_t)N * K, 256);
-    selfbuf = o; o = align_up(o + 32 * (size_t)N, 256);
-  }
-  total = o;
 }
 
 void launch_neighbor_forward(const NeighborArgs& a, float* losses, void* ws, hipStream_t s) {
@@ -528,4 +538,113 @@ void launch_neighbor_rev_ptr(int64_t NK, int64_t N, const uint64_t* keys, const 
                      rev_pair, rev_pos);
 }
 
+// Scratch of gs_neighbor_reverse: the (neighbour id, pair) keys and the radix
+// sort's own scratch.
+struct RevLayout {
+  size_t keys, vals, status, sort, total;
+  explicit RevLayout(int64_t NK) {
+    size_t o = 0;
+    keys = o; o = align_up(o + 8 * (size_t)NK, 256);
+    vals = o; o = align_up(o + 4 * (size_t)NK, 256);
+    status = o; o = align_up(o + 4, 256);
+    sort = o; o = align_up(o + SortLayout(NK).total, 256);
+    total = o;
+  }
+};
+
+int check_graph(const gs_neighbor_graph* g, bool backward, NeighborArgs* a) {
+  if (!g) return gs_set_error(-1, "null neighbour graph");
+  if (g->N < 0 || g->K < 0) return gs_set_error(-1, "N and K must be >= 0 (got N=%lld K=%d)", (long long)g->N, g->K);
+  if ((double)g->N * g->K >= 2147483647.0)
+    return gs_set_error(-1, "N*K must fit in int32 (got N=%lld K=%d)", (long long)g->N, g->K);
+  if (g->N > 0 && (!g->prev_inv_rot || (g->K > 0 && (!g->nbr || !g->weight || !g->dist || !g->prev_offset))))
+    return gs_set_error(-1, "neighbour graph arrays are required");
+  if (backward && g->N > 0 && (!g->rev_ptr || (g->K > 0 && !g->rev_pos)))
+    return gs_set_error(-1, "the backward needs the reverse CSR (gs_neighbor_reverse)");
+  *a = NeighborArgs{g->N, g->K, nullptr, nullptr, g->nbr, g->weight, g->dist, g->prev_offset, g->prev_inv_rot,
+                    g->rev_ptr, g->rev_pos};
+  return 0;
+}
+
+}  // namespace
+
 }  // namespace gs
+
+using namespace gs;
+
+// ---- the C ABI (include/gs_neighbor.h) ----
+
+extern "C" {
+
+size_t gs_neighbor_workspace_bytes(int64_t N, int32_t K, int backward) {
+  return NeighborLayout(N < 0 ? 0 : N, K < 0 ? 0 : K, backward != 0).total;
+}
+
+int gs_neighbor_loss_forward(const gs_neighbor_graph* g, const float* fg_pts, const float* fg_rot, float* losses,
+                             void* workspace, gs_stream_t stream) {
+  NeighborArgs a;
+  if (int e = check_graph(g, false, &a)) return e;
+  if (!losses || !workspace) return gs_set_error(-1, "losses and workspace are required");
+  if (a.N > 0 && (!fg_pts || !fg_rot)) return gs_set_error(-1, "fg_pts and fg_rot are required");
+  a.fg_pts = fg_pts;
+  a.fg_rot = fg_rot;
+  hipStream_t s = (hipStream_t)stream;
+  launch_neighbor_forward(a, losses, workspace, s);
+  return launch_status("neighbour loss forward", 0, s);
+}
+
+int gs_neighbor_loss_backward(const gs_neighbor_graph* g, const float* fg_pts, const float* fg_rot,
+                              const float* dL_dlosses, float* d_fg_pts, float* d_fg_rot, void* workspace,
+                              gs_stream_t stream) {
+  NeighborArgs a;
+  if (int e = check_graph(g, true, &a)) return e;
+  if (a.N == 0) return 0;
+  if (!fg_pts || !fg_rot || !dL_dlosses || !d_fg_pts || !d_fg_rot || !workspace)
+    return gs_set_error(-1, "neighbour loss backward: null argument");
+  a.fg_pts = fg_pts;
+  a.fg_rot = fg_rot;
+  hipStream_t s = (hipStream_t)stream;
+  launch_neighbor_backward(a, dL_dlosses, d_fg_pts, d_fg_rot, workspace, s);
+  return launch_status("neighbour loss backward", 0, s);
+}
+
+size_t gs_neighbor_reverse_workspace_bytes(int64_t N, int32_t K) {
+  return RevLayout((N < 0 ? 0 : N) * (K < 0 ? 0 : K)).total;
+}
+
+int gs_neighbor_reverse(int64_t N, int32_t K, const int64_t* nbr, int32_t* rev_ptr, int32_t* rev_pair,
+                        int32_t* rev_pos, void* workspace, gs_stream_t stream) {
+  if (N < 0 || K < 0) return gs_set_error(-1, "N and K must be >= 0");
+  if ((double)N * K >= 2147483647.0) return gs_set_error(-1, "N*K must fit in int32");
+  const int64_t NK = N * K;
+  if (!rev_ptr || !workspace || (NK > 0 && (!nbr || !rev_pos)))
+    return gs_set_error(-1, "neighbour reverse: null argument");
+  hipStream_t s = (hipStream_t)stream;
+  const RevLayout L(NK);
+  uint64_t* keys = at<uint64_t>(workspace, L.keys);
+  uint32_t* vals = at<uint32_t>(workspace, L.vals);
+  int* status = at<int>(workspace, L.status);
+  (void)hipMemsetAsync(status, 0, 4, s);
+  launch_neighbor_rev_keys(NK, N, nbr, keys, vals, status, s);
+  if (NK > 1) {
+    const SortLayout sl(NK);
+    void* sc = at<char>(workspace, L.sort);
+    uint64_t* k1 = at<uint64_t>(sc, sl.keys1);
+    uint32_t* v1 = at<uint32_t>(sc, sl.vals1);
+    int end_bit = 1;  // keys <= N (N marks invalid ids)
+    while (end_bit < 63 && ((uint64_t)N >> end_bit)) ++end_bit;
+    if (launch_radix_sort(NK, keys, vals, k1, v1, at<uint32_t>(sc, sl.hist), at<uint32_t>(sc, sl.rowtot),
+                          end_bit, s)) {
+      keys = k1;
+      vals = v1;
+    }
+  }
+  launch_neighbor_rev_ptr(NK, N, keys, vals, rev_ptr, rev_pair, rev_pos, s);
+  int host_status = 0;
+  (void)hipMemcpyAsync(&host_status, status, 4, hipMemcpyDeviceToHost, s);
+  if (int e = launch_status("neighbour reverse", 1, s)) return e;
+  if (host_status) return gs_set_error(-1, "neighbor_indices out of range [0, %lld)", (long long)N);
+  return 0;
+}
+
+}  // extern "C"

@@ -12,7 +12,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/gs_optim.h"
-#include "gs_kernels.h"
+#include "gs_launch.h"
 
 namespace gs {
 
@@ -94,8 +94,6 @@ __global__ void __launch_bounds__(OPT_THREADS) adam_stats_kernel(const AdamTable
   }
 }
 
-}  // namespace
-
 bool launch_adam_step(const gs_adam_args& a, const gs_densify_stats* st, hipStream_t s) {
   AdamTable T{};
   T.a = a;
@@ -121,4 +119,29 @@ bool launch_adam_step(const gs_adam_args& a, const gs_densify_stats* st, hipStre
   return true;
 }
 
+}  // namespace
+
 }  // namespace gs
+
+using namespace gs;
+
+extern "C" int gs_adam_step(const gs_adam_args* a, const gs_densify_stats* st, gs_stream_t stream) {
+  if (!a) return gs_set_error(-1, "null Adam arguments");
+  if (a->n_tensors < 0 || a->n_tensors > GS_ADAM_MAX_TENSORS)
+    return gs_set_error(-1, "n_tensors must be in [0, %d] (got %d)", GS_ADAM_MAX_TENSORS, a->n_tensors);
+  for (int t = 0; t < a->n_tensors; ++t) {
+    const gs_adam_tensor& x = a->t[t];
+    if (x.numel < 0) return gs_set_error(-1, "tensor %d: numel < 0", t);
+    if (x.numel > 0 && (!x.param || !x.grad || !x.exp_avg || !x.exp_avg_sq))
+      return gs_set_error(-1, "tensor %d: param, grad, exp_avg and exp_avg_sq are required", t);
+    if (!(x.bc2_sqrt > 0.f)) return gs_set_error(-1, "tensor %d: bc2_sqrt must be > 0 (step >= 1)", t);
+  }
+  if (st && st->P > 0) {
+    if (!st->radii) return gs_set_error(-1, "densify stats: radii are required");
+    if (st->grad_accum && (!st->denom || !st->means2D_grad))
+      return gs_set_error(-1, "densify stats: grad_accum needs denom and means2D_grad");
+  }
+  hipStream_t s = (hipStream_t)stream;
+  if (!launch_adam_step(*a, st, s)) return gs_set_error(-1, "Adam step: too many blocks");
+  return launch_status("adam step", 0, s);
+}

@@ -128,6 +128,7 @@ __global__ __launch_bounds__(TB_THREADS) void tile_hist_kernel(TileArgs a0, CamB
   if (!WRITE) {
     // the reference's num_rendered: bounding-rect instances of this block
     // (counted once, in the first tile pass)
+    // (open-coded: through wave_sum the compiler lays this kernel's walk loop out differently)
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) rect_n += __shfl_xor(rect_n, o, 64);
     if (lane == 0) s_rect[tid >> 6] = rect_n;
@@ -179,12 +180,7 @@ __global__ __launch_bounds__(TB_THREADS) void tile_count_kernel(TileArgs a0, Cam
     uint32_t carry = 0;
     for (int c0 = 0; c0 < n; c0 += 64) {
       const int i = c0 + lane;
-      uint32_t v = i < n ? s_d[base + i * step] : 0u;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t t = __shfl_up(v, o, 64);
-        if (lane >= o) v += t;
-      }
+      const uint32_t v = wave_incl_scan(i < n ? s_d[base + i * step] : 0u, lane);
       if (i < n) s_d[base + i * step] = v + carry;
       carry += __shfl(v, 63, 64);
     }
@@ -199,8 +195,7 @@ __global__ __launch_bounds__(TB_THREADS) void tile_count_kernel(TileArgs a0, Cam
     a.thist[(size_t)b * T + t] = s_d[y * DX + x];
   }
   // the reference's num_rendered: bounding-rect instances of this block
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) rect_n += __shfl_xor(rect_n, o, 64);
+  rect_n = wave_sum(rect_n);
   if (lane == 0) s_rect[wv] = rect_n;
   __syncthreads();
   if (tid == 0) {
@@ -258,12 +253,7 @@ __global__ __launch_bounds__(TB_THREADS) void tile_bucket_kernel(TileArgs a0, Ca
     }
   }
   // exclusive scan of the per-thread sums over the block
-  uint32_t incl = run;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t y = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += y;
-  }
+  const uint32_t incl = wave_incl_scan(run, lane);
   if (lane == 63) s_wsum[wv] = incl;
   __syncthreads();
   if (tid == 0) {
@@ -417,20 +407,13 @@ __global__ __launch_bounds__(OFF_T) void tile_offsets_kernel(const uint32_t* __r
     mx = max(mx, v);
   }
   // wave inclusive scan, then across the 16 waves
-  unsigned long long inc = sum;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const unsigned long long y = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += y;
-  }
+  const unsigned long long inc = wave_incl_scan(sum, lane);
   if (lane == 63) s_sum[wave] = inc;
   __syncthreads();
   atomicMax(&s_max, mx);
   // the reference's num_rendered: sum of the per-block tiles_touched sums
   if (tid < TB_BLOCKS) {
-    unsigned long long v = bsum[tid];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    const unsigned long long v = wave_sum<unsigned long long>(bsum[tid]);
     if (lane == 0) atomicAdd(&s_lref, v);
   }
   __syncthreads();  // s_max complete (read by the sort-class counts below)
@@ -544,12 +527,7 @@ __global__ __launch_bounds__(OFF_T) void tile_order_kernel(const uint32_t* __res
   for (int t = a0; t < a1; ++t) atomicAdd(&s_obin[OFF_T - 1 - min(ttotal[t] >> sh, (uint32_t)(OFF_T - 1))], 1u);
   __syncthreads();
   const uint32_t c = s_obin[tid];
-  uint32_t ci = c;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t y = __shfl_up(ci, o, 64);
-    if (lane >= o) ci += y;
-  }
+  const uint32_t ci = wave_incl_scan(c, lane);
   if (lane == 63) s_owsum[wave] = ci;
   __syncthreads();
   uint32_t base = ci - c;
@@ -655,12 +633,7 @@ __device__ __attribute__((always_inline)) KP tile_radix_sort(KP A, KP B, int n, 
         tot += c[w];
       }
       if (tot == (uint32_t)n) sm.skip = 1;
-      inc = tot;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t y = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += y;
-      }
+      inc = wave_incl_scan(tot, lane);
       if (lane == 63) sm.wsum[wave] = inc;
     }
     __syncthreads();
@@ -792,12 +765,7 @@ __device__ __attribute__((always_inline)) bool tile_bucket_sort(const uint64_t* 
     run += c[b];
     crowded = crowded || c[b] > (uint32_t)BS_BUCKET_MAX;
   }
-  uint32_t inc = run;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t y = __shfl_up(inc, o, 64);
-    if (lane >= o) inc += y;
-  }
+  const uint32_t inc = wave_incl_scan(run, lane);
   if (lane == 63) wsum[wave] = inc;
   if (crowded) sm.skip = 1;
   __syncthreads();

@@ -60,10 +60,6 @@ def schedule(i: int) -> dict:
             "reset": active and i > 0 and i % RESET_EVERY == 0}
 
 
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
 def _need(t, name: str, rows: Optional[int] = None) -> torch.Tensor:
     if not isinstance(t, torch.Tensor):
         raise GsplatError(f"{name} must be a tensor")
@@ -154,7 +150,7 @@ def _accumulate_hip(variables: dict):
     st = _lib.GsDensifyStats(P=P, radii=radii.data_ptr(), means2D_grad=g.data_ptr(), max_radius=None,
                              grad_accum=acc.data_ptr(), denom=den.data_ptr())
     args = _lib.GsAdamArgs(n_tensors=0, beta1=0.9, beta2=0.999, eps=1e-8)
-    _lib.check(_lib.load().gs_adam_step(ctypes.byref(args), ctypes.byref(st), _stream(seen.device)),
+    _lib.check(_lib.load().gs_adam_step(ctypes.byref(args), ctypes.byref(st), _lib.stream(seen.device)),
                "densify accumulate")
 
 
@@ -177,7 +173,7 @@ def plan(grad_accum, denom, log_scales, logit_opacities, *, grad_thresh, clone_m
                                   grad_thresh=grad_thresh, clone_max_scale=clone_max_scale,
                                   prune_min_opacity=prune_min_opacity, prune_max_scale=prune_max_scale,
                                   n_split=N_SPLIT, workspace=ws.data_ptr(), workspace_bytes=ws.numel())
-    _lib.check(L.gs_densify_plan(ctypes.byref(args), _stream(dev)), "densify plan")
+    _lib.check(L.gs_densify_plan(ctypes.byref(args), _lib.stream(dev)), "densify plan")
     if P == 0:
         return ws, [0, 0, 0, 0]
     off = L.gs_densify_counts_offset(P)
@@ -249,7 +245,7 @@ def _hip_pass(params, variables, optimizer, sch, noise, generator, grad_thresh):
         tk.dst, tk.dst_exp_avg, tk.dst_exp_avg_sq = p(dst), p(dm), p(dv)
         tk.width, tk.role = width, _lib.GS_DENSIFY_ROLES[ROLE_OF.get(k, "plain")]
         outs.append((k, src, m, v, dst, dm, dv))
-    _lib.check(L.gs_densify_apply(ctypes.byref(args), _stream(dev)), "densify apply")
+    _lib.check(L.gs_densify_apply(ctypes.byref(args), _lib.stream(dev)), "densify apply")
     for k, _src, _m, _v, dst, dm, dv in outs:
         _install(params, optimizer, k, dst, dm, dv)
     for name, t in zip(STATS, new_stats):

@@ -620,7 +620,7 @@ class ShardedAdam:
         for j, (_, _, _, _, step_size, bc2s) in enumerate(entries):
             args.t[j].step_size, args.t[j].bc2_sqrt = step_size, bc2s
         _lib.check(_lib.load().gs_adam_step(ctypes.byref(args), None,
-                                            torch.cuda.current_stream(self.param_flat.device).cuda_stream),
+                                            _lib.stream(self.param_flat.device)),
                    "sharded adam step")
 
     def step(self, k: int = 0, lr: Optional[Mapping[str, float]] = None,

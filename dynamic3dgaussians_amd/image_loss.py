@@ -35,10 +35,6 @@ WINDOW, SIGMA = 11, 1.5
 C1, C2 = 0.01 ** 2, 0.03 ** 2
 
 
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
 def _need(t, name: str, shape=None) -> torch.Tensor:
     if not isinstance(t, torch.Tensor):
         raise GsplatError(f"{name} must be a tensor")
@@ -80,7 +76,7 @@ class _PhotometricLoss(torch.autograd.Function):
         # the derivative maps the backward convolves live here (torch's caching allocator)
         ws = torch.empty(L.gs_photo_loss_workspace_bytes(B, Ch, H, W), dtype=torch.uint8, device=dev)
         args = _struct(image, target, mask, gain, offset, l1_weight, ssim_weight, losses, ws)
-        _lib.check(L.gs_photo_loss_forward(args, _stream(dev)), "photometric loss forward")
+        _lib.check(L.gs_photo_loss_forward(args, _lib.stream(dev)), "photometric loss forward")
         ctx.save_for_backward(image, target, mask, gain, offset, ws)
         ctx.weights = (l1_weight, ssim_weight)
         return losses
@@ -98,7 +94,7 @@ class _PhotometricLoss(torch.autograd.Function):
         args = _struct(image, target, mask, gain, offset, *ctx.weights, up, ws)  # losses: unused by the backward
         _lib.check(L.gs_photo_loss_backward(args, up.data_ptr(), d_image.data_ptr(),
                                             d_gain.data_ptr() if need_corr else None,
-                                            d_offset.data_ptr() if need_corr else None, _stream(dev)),
+                                            d_offset.data_ptr() if need_corr else None, _lib.stream(dev)),
                    "photometric loss backward")
         return d_image, None, None, d_gain, d_offset, None, None
 

@@ -44,7 +44,7 @@ def knn(points: torch.Tensor, k: int):
     L = _lib.load()
     ws = torch.empty(L.gs_knn_workspace_bytes(N), dtype=torch.uint8, device=dev)
     _lib.check(L.gs_knn(N, int(k), pts.data_ptr(), sq.data_ptr(), idx.data_ptr(), ws.data_ptr(),
-                        torch.cuda.current_stream(dev).cuda_stream), "knn")
+                        _lib.stream(dev)), "knn")
     return sq, idx
 
 

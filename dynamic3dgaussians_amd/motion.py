@@ -93,10 +93,6 @@ def motion_positions_torch(means, coefs, rots, transls, ts, softmax: bool = Fals
     return (positions, transfms) if return_transforms else positions
 
 
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
 def _desc(means, coefs, rots, transls, ts, softmax):
     G, K = coefs.shape
     d = _lib.GsMotionDesc(G=G, K=K, T=rots.shape[1], B=len(ts), coef_mode=1 if softmax else 0,
@@ -123,7 +119,7 @@ class _MotionWarp(torch.autograd.Function):
         if G:  # an empty output has no address to hand over, and there is nothing to launch
             desc = _desc(means, coefs, rots, transls, ts, softmax)
             _lib.check(L.gs_motion_forward(desc, out.data_ptr() if means is not None else None,
-                                           out.data_ptr() if means is None else None, None, _stream(dev)),
+                                           out.data_ptr() if means is None else None, None, _lib.stream(dev)),
                        "motion forward")
         ctx.save_for_backward(means, coefs, rots, transls)
         ctx.ts, ctx.softmax = ts, softmax
@@ -145,7 +141,7 @@ class _MotionWarp(torch.autograd.Function):
         _lib.check(L.gs_motion_backward(desc, g_out.data_ptr() if means is not None else None,
                                         g_out.data_ptr() if means is None else None,
                                         d_means.data_ptr() if want_means else None, d_coefs.data_ptr(),
-                                        d_rots.data_ptr(), d_transls.data_ptr(), ws.data_ptr(), _stream(dev)),
+                                        d_rots.data_ptr(), d_transls.data_ptr(), ws.data_ptr(), _lib.stream(dev)),
                    "motion backward")
         return d_means, d_coefs, d_rots, d_transls, None, None
 

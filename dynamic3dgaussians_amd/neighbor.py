@@ -37,10 +37,6 @@ def _ptr(t):
     return t.data_ptr() if t is not None and t.numel() else None
 
 
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
 def _need(t: torch.Tensor, name: str, dtype, shape) -> torch.Tensor:
     if not isinstance(t, torch.Tensor):
         raise TypeError(f"{name} must be a tensor")
@@ -69,7 +65,7 @@ def reverse_csr(neighbor_indices: torch.Tensor):
     rev_pos = torch.empty(N * K, dtype=torch.int32, device=dev)
     ws = torch.empty(L.gs_neighbor_reverse_workspace_bytes(N, K), dtype=torch.uint8, device=dev)
     _lib.check(L.gs_neighbor_reverse(N, K, _ptr(nbr), rev_ptr.data_ptr(), _ptr(rev_pair), _ptr(rev_pos),
-                                     ws.data_ptr(), _stream(dev)), "neighbor reverse")
+                                     ws.data_ptr(), _lib.stream(dev)), "neighbor reverse")
     return rev_ptr, rev_pair, rev_pos
 
 
@@ -117,7 +113,7 @@ class _NeighborLosses(torch.autograd.Function):
         ws = torch.empty(L.gs_neighbor_workspace_bytes(graph.N, graph.K, 0), dtype=torch.uint8, device=dev)
         g = graph.struct()
         _lib.check(L.gs_neighbor_loss_forward(g, _ptr(pts), _ptr(rot), out.data_ptr(), ws.data_ptr(),
-                                              _stream(dev)), "neighbor loss forward")
+                                              _lib.stream(dev)), "neighbor loss forward")
         ctx.graph = graph
         ctx.save_for_backward(pts, rot)
         return out[0], out[1], out[2]
@@ -134,7 +130,7 @@ class _NeighborLosses(torch.autograd.Function):
         d_rot = torch.empty_like(rot)
         ws = torch.empty(L.gs_neighbor_workspace_bytes(graph.N, graph.K, 1), dtype=torch.uint8, device=dev)
         _lib.check(L.gs_neighbor_loss_backward(graph.struct(), _ptr(pts), _ptr(rot), dL.data_ptr(),
-                                               _ptr(d_pts), _ptr(d_rot), ws.data_ptr(), _stream(dev)),
+                                               _ptr(d_pts), _ptr(d_rot), ws.data_ptr(), _lib.stream(dev)),
                    "neighbor loss backward")
         return d_pts, d_rot, None
 

@@ -35,10 +35,6 @@ from . import _lib
 MAX_TENSORS = 16
 
 
-def _stream(dev):
-    return torch.cuda.current_stream(dev).cuda_stream
-
-
 def _stats_struct(variables: dict, radius: torch.Tensor, accumulate: bool):
     P = radius.numel()
     if not radius.is_cuda or radius.dtype != torch.int32:
@@ -71,7 +67,7 @@ def densify_stats(variables: dict, radius: torch.Tensor, accumulate: bool = True
     (external.py:136-140) -- one launch.  Also sets variables['seen']."""
     st, keep = _stats_struct(variables, radius, accumulate)
     args = _lib.GsAdamArgs(n_tensors=0, beta1=0.9, beta2=0.999, eps=1e-8)
-    _lib.check(_lib.load().gs_adam_step(ctypes.byref(args), ctypes.byref(st), _stream(radius.device)),
+    _lib.check(_lib.load().gs_adam_step(ctypes.byref(args), ctypes.byref(st), _lib.stream(radius.device)),
                "densify stats")
     variables["seen"] = radius > 0
     del keep
@@ -147,7 +143,7 @@ class FusedAdam(torch.optim.Optimizer):
         if dev is None:
             return loss
         L = _lib.load()
-        stream = _stream(dev)
+        stream = _lib.stream(dev)
         first = True
         for b in range(0, max(len(entries), 1), MAX_TENSORS):
             chunk = entries[b:b + MAX_TENSORS]

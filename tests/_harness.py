@@ -3,6 +3,8 @@ seeded inputs and compare.  The oracle is used here only as the checker."""
 from __future__ import annotations
 
 import ctypes
+import os
+import subprocess
 
 import numpy as np
 import torch
@@ -13,6 +15,7 @@ from dynamic3dgaussians_amd.scene import make_gaussians
 from oracle import oracle as O
 
 DEV = "cuda"
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def scene(P=2000, F=0, sh_degree=0, seed=0, W=128, H=96, cam_index=0, use_sh=False,
@@ -231,6 +234,29 @@ def covers_pixels(st_o, radii, pixels, W):
         px, py = float(p % W), float(p // W)
         hit |= (r > 0) & (np.abs(m2[:, 0] - px) <= r + 1) & (np.abs(m2[:, 1] - py) <= r + 1)
     return hit
+
+
+def run_host_sanitizer(tmp_path, driver_c, host_cpps, ok_line):
+    """Build tools/<driver_c> (C, its own main) with csrc/<host_cpps> (host-only C++) under
+    ASan + UBSan into a plain CPU executable and run it: nothing preloaded, nothing loaded
+    into Python.  Passes when it exits 0, prints `ok_line` and no sanitizer reports."""
+    san = ["-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
+    csrc = os.path.join(REPO, "dynamic3dgaussians_amd", "csrc")
+    inc = ["-I", os.path.join(REPO, "include"), "-I", csrc]
+    objs = []
+    for cc, std, src in [("gcc", "-std=c11", os.path.join(REPO, "tools", driver_c)),
+                         *(("g++", "-std=c++17", os.path.join(csrc, f)) for f in host_cpps)]:
+        obj = str(tmp_path / (os.path.basename(src) + ".o"))
+        subprocess.run([cc, *san, std, "-Wall", "-Wextra", *inc, "-c", src, "-o", obj], check=True,
+                       capture_output=True, timeout=300)
+        objs.append(obj)
+    exe = str(tmp_path / os.path.splitext(driver_c)[0])
+    subprocess.run(["g++", *san, "-o", exe, *objs, "-lm"], check=True, capture_output=True, timeout=300)
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120, env=env)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    assert ok_line in r.stdout
+    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-4000:]
 
 
 def psnr(a, b, peak=1.0):

@@ -27,6 +27,7 @@ import torch
 
 from dynamic3dgaussians_amd import _lib, densify, densify_torch
 from tests import _densify_cases as C
+from tests._harness import run_host_sanitizer
 
 D = importlib.import_module("dynamic3dgaussians_amd.densify")
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -424,21 +425,5 @@ def test_wrapper_rejects_what_the_kernels_cannot_take():
 def test_validators_are_sanitizer_clean(tmp_path):
     """gs_densify_host.cpp (with gs_host.cpp's error state) under ASan + UBSan in a plain CPU
     executable with its own main: nothing preloaded, nothing loaded into Python."""
-    san = ["-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
-    csrc = os.path.join(REPO, "dynamic3dgaussians_amd", "csrc")
-    inc = ["-I", os.path.join(REPO, "include"), "-I", csrc]
-    objs = []
-    for cc, std, src in [("gcc", "-std=c11", os.path.join(REPO, "tools", "densify_host_sanitize.c")),
-                         ("g++", "-std=c++17", os.path.join(csrc, "gs_densify_host.cpp")),
-                         ("g++", "-std=c++17", os.path.join(csrc, "gs_host.cpp"))]:
-        obj = str(tmp_path / (os.path.basename(src) + ".o"))
-        subprocess.run([cc, *san, std, "-Wall", "-Wextra", *inc, "-c", src, "-o", obj], check=True,
-                       capture_output=True, timeout=300)
-        objs.append(obj)
-    exe = str(tmp_path / "densify_host_sanitize")
-    subprocess.run(["g++", *san, "-o", exe, *objs, "-lm"], check=True, capture_output=True, timeout=300)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120, env=env)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    assert "densify host sanitize ok" in r.stdout
-    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-4000:]
+    run_host_sanitizer(tmp_path, "densify_host_sanitize.c", ["gs_densify_host.cpp", "gs_host.cpp"],
+                       "densify host sanitize ok")

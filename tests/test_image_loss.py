@@ -22,6 +22,7 @@ import torch
 
 from dynamic3dgaussians_amd import _lib, image_loss
 from dynamic3dgaussians_amd import photometric_image_loss, photometric_loss, photometric_loss_torch
+from tests._harness import run_host_sanitizer
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(REPO, "tests", "golden", "photometric_loss.npz")
@@ -225,21 +226,5 @@ class _DeviceClaim(torch.Tensor):
 def test_validator_is_sanitizer_clean(tmp_path):
     """gs_loss_host.cpp (with gs_host.cpp's error state) under ASan + UBSan in a plain CPU
     executable with its own main: nothing preloaded, nothing loaded into Python."""
-    san = ["-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
-    csrc = os.path.join(REPO, "dynamic3dgaussians_amd", "csrc")
-    inc = ["-I", os.path.join(REPO, "include"), "-I", csrc]
-    objs = []
-    for cc, std, src in [("gcc", "-std=c11", os.path.join(REPO, "tools", "loss_host_sanitize.c")),
-                         ("g++", "-std=c++17", os.path.join(csrc, "gs_loss_host.cpp")),
-                         ("g++", "-std=c++17", os.path.join(csrc, "gs_host.cpp"))]:
-        obj = str(tmp_path / (os.path.basename(src) + ".o"))
-        subprocess.run([cc, *san, std, "-Wall", "-Wextra", *inc, "-c", src, "-o", obj], check=True,
-                       capture_output=True, timeout=300)
-        objs.append(obj)
-    exe = str(tmp_path / "loss_host_sanitize")
-    subprocess.run(["g++", *san, "-o", exe, *objs, "-lm"], check=True, capture_output=True, timeout=300)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120, env=env)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    assert "loss host sanitize ok" in r.stdout
-    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-4000:]
+    run_host_sanitizer(tmp_path, "loss_host_sanitize.c", ["gs_loss_host.cpp", "gs_host.cpp"],
+                       "loss host sanitize ok")

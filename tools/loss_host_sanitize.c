@@ -8,25 +8,14 @@
  * validator may dereference.  Exit status 0 and "loss host sanitize ok" on
  * success. */
 #include <math.h>
-#include <stdio.h>
 #include <stdlib.h>
-#include <string.h>
 
 #include "gs_loss.h"
+#include "host_sanitize.h"
 
-static int failures = 0;
-
-static void expect(int ok, const char *what) {
-  if (!ok) {
-    fprintf(stderr, "FAIL: %s (last error: %s)\n", what, gs_last_error());
-    ++failures;
-  }
-}
-
-static int refused(const gs_photo_loss *a, int backward, const float *up, const float *di, const float *dg,
-                   const float *dofs, const char *needle) {
-  const int code = gs_photo_loss_validate(a, backward, up, di, dg, dofs);
-  return code < 0 && strstr(gs_last_error(), needle) != NULL;
+static int loss_refused(const gs_photo_loss *a, int backward, const float *up, const float *di, const float *dg,
+                        const float *dofs, const char *needle) {
+  return refused(gs_photo_loss_validate(a, backward, up, di, dg, dofs), needle);
 }
 
 int main(void) {
@@ -67,31 +56,31 @@ int main(void) {
 
   /* invalid blocks, one fault each */
   gs_photo_loss bad;
-  expect(refused(NULL, 0, NULL, NULL, NULL, NULL, "null argument block"), "null block");
-  bad = good; bad.B = 0;   expect(refused(&bad, 0, NULL, NULL, NULL, NULL, "must be > 0"), "B = 0");
-  bad = good; bad.Ch = -3; expect(refused(&bad, 0, NULL, NULL, NULL, NULL, "must be > 0"), "Ch < 0");
-  bad = good; bad.H = 0;   expect(refused(&bad, 0, NULL, NULL, NULL, NULL, "must be > 0"), "H = 0");
-  bad = good; bad.W = -1;  expect(refused(&bad, 0, NULL, NULL, NULL, NULL, "must be > 0"), "W < 0");
-  bad = good; bad.image = NULL;  expect(refused(&bad, 0, NULL, NULL, NULL, NULL, "required"), "null image");
-  bad = good; bad.target = NULL; expect(refused(&bad, 0, NULL, NULL, NULL, NULL, "required"), "null target");
-  bad = good; bad.losses = NULL; expect(refused(&bad, 0, NULL, NULL, NULL, NULL, "required"), "null losses");
+  expect(loss_refused(NULL, 0, NULL, NULL, NULL, NULL, "null argument block"), "null block");
+  bad = good; bad.B = 0;   expect(loss_refused(&bad, 0, NULL, NULL, NULL, NULL, "must be > 0"), "B = 0");
+  bad = good; bad.Ch = -3; expect(loss_refused(&bad, 0, NULL, NULL, NULL, NULL, "must be > 0"), "Ch < 0");
+  bad = good; bad.H = 0;   expect(loss_refused(&bad, 0, NULL, NULL, NULL, NULL, "must be > 0"), "H = 0");
+  bad = good; bad.W = -1;  expect(loss_refused(&bad, 0, NULL, NULL, NULL, NULL, "must be > 0"), "W < 0");
+  bad = good; bad.image = NULL;  expect(loss_refused(&bad, 0, NULL, NULL, NULL, NULL, "required"), "null image");
+  bad = good; bad.target = NULL; expect(loss_refused(&bad, 0, NULL, NULL, NULL, NULL, "required"), "null target");
+  bad = good; bad.losses = NULL; expect(loss_refused(&bad, 0, NULL, NULL, NULL, NULL, "required"), "null losses");
   bad = good; bad.image = (const float *)((const char *)image + 1);
-  expect(refused(&bad, 0, NULL, NULL, NULL, NULL, "4-byte aligned"), "misaligned image");
+  expect(loss_refused(&bad, 0, NULL, NULL, NULL, NULL, "4-byte aligned"), "misaligned image");
   bad = good; bad.target = (const float *)((const char *)target + 2);
-  expect(refused(&bad, 0, NULL, NULL, NULL, NULL, "4-byte aligned"), "misaligned target");
+  expect(loss_refused(&bad, 0, NULL, NULL, NULL, NULL, "4-byte aligned"), "misaligned target");
   bad = good; bad.workspace = NULL;
-  expect(refused(&bad, 0, NULL, NULL, NULL, NULL, "workspace is required"), "null workspace");
+  expect(loss_refused(&bad, 0, NULL, NULL, NULL, NULL, "workspace is required"), "null workspace");
   bad = good; bad.workspace_bytes = ws_bytes - 1;
-  expect(refused(&bad, 0, NULL, NULL, NULL, NULL, "needed"), "short workspace");
+  expect(loss_refused(&bad, 0, NULL, NULL, NULL, NULL, "needed"), "short workspace");
   bad = good; bad.l1_weight = NAN;
-  expect(refused(&bad, 0, NULL, NULL, NULL, NULL, "finite"), "NaN l1_weight");
+  expect(loss_refused(&bad, 0, NULL, NULL, NULL, NULL, "finite"), "NaN l1_weight");
   bad = good; bad.ssim_weight = INFINITY;
-  expect(refused(&bad, 0, NULL, NULL, NULL, NULL, "finite"), "infinite ssim_weight");
+  expect(loss_refused(&bad, 0, NULL, NULL, NULL, NULL, "finite"), "infinite ssim_weight");
   bad = full; bad.mask_batch_stride = 7;
-  expect(refused(&bad, 0, NULL, NULL, NULL, NULL, "mask_batch_stride"), "odd mask stride");
-  expect(refused(&good, 1, NULL, d_image, NULL, NULL, "dL_dloss"), "backward without dL_dloss");
-  expect(refused(&good, 1, up, NULL, NULL, NULL, "dL_dimage"), "backward without dL_dimage");
-  expect(refused(&good, 1, up, (const float *)((const char *)d_image + 3), NULL, NULL, "4-byte aligned"),
+  expect(loss_refused(&bad, 0, NULL, NULL, NULL, NULL, "mask_batch_stride"), "odd mask stride");
+  expect(loss_refused(&good, 1, NULL, d_image, NULL, NULL, "dL_dloss"), "backward without dL_dloss");
+  expect(loss_refused(&good, 1, up, NULL, NULL, NULL, "dL_dimage"), "backward without dL_dimage");
+  expect(loss_refused(&good, 1, up, (const float *)((const char *)d_image + 3), NULL, NULL, "4-byte aligned"),
          "misaligned dL_dimage");
 
   free(image); free(target); free(d_image); free(mask); free(gain); free(offset); free(d_gain); free(d_offset);

@@ -6,24 +6,13 @@
  * each one with a message and touch nothing they were not given.  The
  * pointers name heap buffers of the right size, none of which a validator may
  * dereference.  Exit status 0 and "motion host sanitize ok" on success. */
-#include <stdio.h>
 #include <stdlib.h>
-#include <string.h>
 
 #include "gs_motion.h"
-
-static int failures = 0;
-
-static void expect(int ok, const char *what) {
-  if (!ok) {
-    fprintf(stderr, "FAIL: %s (last error: %s)\n", what, gs_last_error());
-    ++failures;
-  }
-}
+#include "host_sanitize.h"
 
 static int fwd_refused(const gs_motion_desc *d, const float *pos, const float *tf, const char *needle) {
-  const int code = gs_motion_forward_validate(d, pos, tf, NULL);
-  return code < 0 && strstr(gs_last_error(), needle) != NULL;
+  return refused(gs_motion_forward_validate(d, pos, tf, NULL), needle);
 }
 
 int main(void) {
@@ -97,21 +86,21 @@ int main(void) {
   expect(fwd_refused(&good, (const float *)((const char *)pos + 1), NULL, "4-byte aligned"), "misaligned positions");
   expect(gs_motion_forward_validate(&good, NULL, tf + 1, NULL) == 0, "transforms need no 16-byte alignment");
 
-  expect(gs_motion_backward_validate(&good, NULL, NULL, d_means, d_coefs, d_rots, d_transls, ws) < 0 &&
-             strstr(gs_last_error(), "d_positions or d_transforms"), "backward without an upstream gradient");
-  expect(gs_motion_backward_validate(&good, pos, NULL, d_means, NULL, d_rots, d_transls, ws) < 0 &&
-             strstr(gs_last_error(), "d_coefs"), "backward without d_coefs");
-  expect(gs_motion_backward_validate(&good, pos, NULL, d_means, d_coefs, NULL, d_transls, ws) < 0 &&
-             strstr(gs_last_error(), "d_rots"), "backward without d_rots");
-  expect(gs_motion_backward_validate(&good, pos, NULL, d_means, d_coefs, d_rots, d_transls, NULL) < 0 &&
-             strstr(gs_last_error(), "workspace is required"), "backward without workspace");
-  expect(gs_motion_backward_validate(&good, pos, NULL, d_means, d_coefs, d_rots, d_transls, (char *)ws + 4) < 0 &&
-             strstr(gs_last_error(), "16-byte"), "misaligned workspace");
-  expect(gs_motion_backward_validate(&good, pos, NULL, d_means, (float *)((char *)d_coefs + 3), d_rots, d_transls, ws) < 0 &&
-             strstr(gs_last_error(), "4-byte aligned"), "misaligned d_coefs");
+  expect(refused(gs_motion_backward_validate(&good, NULL, NULL, d_means, d_coefs, d_rots, d_transls, ws),
+                 "d_positions or d_transforms"), "backward without an upstream gradient");
+  expect(refused(gs_motion_backward_validate(&good, pos, NULL, d_means, NULL, d_rots, d_transls, ws), "d_coefs"),
+         "backward without d_coefs");
+  expect(refused(gs_motion_backward_validate(&good, pos, NULL, d_means, d_coefs, NULL, d_transls, ws), "d_rots"),
+         "backward without d_rots");
+  expect(refused(gs_motion_backward_validate(&good, pos, NULL, d_means, d_coefs, d_rots, d_transls, NULL),
+                 "workspace is required"), "backward without workspace");
+  expect(refused(gs_motion_backward_validate(&good, pos, NULL, d_means, d_coefs, d_rots, d_transls, (char *)ws + 4),
+                 "16-byte"), "misaligned workspace");
+  expect(refused(gs_motion_backward_validate(&good, pos, NULL, d_means, (float *)((char *)d_coefs + 3), d_rots,
+                                             d_transls, ws), "4-byte aligned"), "misaligned d_coefs");
   d = good; d.means = NULL;
-  expect(gs_motion_backward_validate(&d, pos, NULL, NULL, d_coefs, d_rots, d_transls, ws) < 0 &&
-             strstr(gs_last_error(), "needs means"), "d_positions without means");
+  expect(refused(gs_motion_backward_validate(&d, pos, NULL, NULL, d_coefs, d_rots, d_transls, ws), "needs means"),
+         "d_positions without means");
 
   free(rots); free(transls); free(coefs); free(means); free(pos); free(tf);
   free(d_rots); free(d_transls); free(d_coefs); free(d_means); free(ws);
