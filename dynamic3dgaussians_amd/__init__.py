@@ -11,6 +11,7 @@ Layout:
   scene.py        synthetic scenes for tests and the benchmark
   distributed.py  camera-sharded data parallelism with one RCCL all-reduce
   image_loss.py   the reference's L1 + SSIM photometric loss, fused (include/gs_loss.h)
+  depth_loss.py   the reference's masked depth-correlation (Pearson) loss, fused (include/gs_depth_loss.h)
   densify.py      the reference's clone / split / prune with the Adam state (include/gs_densify.h)
   motion.py       the reference's motion-basis warp: SE(3) basis blend, fused (include/gs_motion.h)
 """
@@ -18,6 +19,7 @@ from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, Grad
                          _RasterizeGaussians, rasterize_gaussians)
 from ._C import set_default_compat, get_default_compat  # noqa: F401
 from .image_loss import photometric_image_loss, photometric_loss, photometric_loss_torch  # noqa: F401
+from .depth_loss import depth_correlation_loss, depth_correlation_loss_torch  # noqa: F401
 # `densify` here is the function; its module (schedule, plan, classify_torch, ...) is
 # importlib.import_module('dynamic3dgaussians_amd.densify')
 from .densify import densify, densify_torch  # noqa: F401

@@ -62,6 +62,14 @@ class GsPhotoLoss(ctypes.Structure):
                 ("losses", c_void_p), ("workspace", c_void_p), ("workspace_bytes", ctypes.c_uint64)]
 
 
+class GsDepthLoss(ctypes.Structure):
+    """include/gs_depth_loss.h gs_depth_loss."""
+    _fields_ = [("B", c_int32), ("H", c_int32), ("W", c_int32), ("depth", c_void_p), ("target", c_void_p),
+                ("mask", c_void_p), ("mask_batch_stride", c_int64), ("near", c_float), ("far", c_float),
+                ("skip_degenerate", c_int32), ("losses", c_void_p), ("stats", c_void_p), ("workspace", c_void_p),
+                ("workspace_bytes", ctypes.c_uint64)]
+
+
 GS_DENSIFY_MAX_TENSORS = 16  # include/gs_densify.h
 GS_DENSIFY_N_SPLIT = 2
 GS_DENSIFY_ROLES = {"plain": 0, "means": 1, "log_scales": 2, "rotations": 3, "logit_opacities": 4}
@@ -203,6 +211,12 @@ PROTOTYPES = {
     "gs_photo_loss_forward": (ctypes.c_int, [ctypes.POINTER(GsPhotoLoss), c_void_p]),
     "gs_photo_loss_backward": (ctypes.c_int, [ctypes.POINTER(GsPhotoLoss), c_void_p, c_void_p, c_void_p,
                                               c_void_p, c_void_p]),
+    # include/gs_depth_loss.h
+    "gs_depth_loss_struct_bytes": (c_size_t, []),
+    "gs_depth_loss_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
+    "gs_depth_loss_validate": (ctypes.c_int, [ctypes.POINTER(GsDepthLoss), ctypes.c_int, c_void_p, c_void_p]),
+    "gs_depth_loss_forward": (ctypes.c_int, [ctypes.POINTER(GsDepthLoss), c_void_p]),
+    "gs_depth_loss_backward": (ctypes.c_int, [ctypes.POINTER(GsDepthLoss), c_void_p, c_void_p, c_void_p]),
     # include/gs_densify.h
     "gs_densify_plan_struct_bytes": (c_size_t, []),
     "gs_densify_tensor_struct_bytes": (c_size_t, []),

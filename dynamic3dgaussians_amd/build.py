@@ -65,11 +65,13 @@ SOURCES = {
     "gs_loss.hip": [],
     "gs_densify.hip": ["-ffp-contract=off"],
     "gs_motion.hip": [],
+    "gs_depth_loss.hip": [],
     "gs_api.hip": [],
     "gs_host.cpp": [],  # host-only C++ (also built by oracle/Makefile's sanitizer target)
     "gs_densify_host.cpp": [],  # host-only C++ (also built into tools/densify_host_sanitize.c's program)
     "gs_loss_host.cpp": [],  # host-only C++ (also built into tools/loss_host_sanitize.c's program)
     "gs_motion_host.cpp": [],  # host-only C++ (also built into tools/motion_host_sanitize.c's program)
+    "gs_depth_loss_host.cpp": [],  # host-only C++ (also built into tools/depth_loss_host_sanitize.c's program)
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall",
           "-Wno-unused-function", "-I", CSRC, "-I", INCLUDE]

@@ -151,14 +151,16 @@ def l1_image_loss(im, target) -> torch.Tensor:
     return torch.abs(im - target).mean(dim=(-3, -2, -1)).sum()
 
 
-def batch_renderer(settings_all: Sequence):
+def batch_renderer(settings_all: Sequence, with_depth: bool = False):
     """The default `render`: GaussianRasterizerBatch over the given cameras
     (one launch per stage), densification statistics tracked.  Returns
     render(rendervar, cams, feature_ready=None) -> (images [C, 3, H, W],
     stats dict or None); with semantic_feature in the rendervar (the G3 call,
     label + features) the images are (colour [C, 3, H, W], features
     [C, F, H, W]) and the blend waits for `feature_ready` (ShardedStep's
-    overlapped feature update) before reading the features."""
+    overlapped feature update) before reading the features.  With
+    `with_depth` the render returns (images, stats, depth [C, 1, H, W]): the
+    rasterizer's depth plane, for `TimestepDriver(depth_loss=...)`."""
     from .rasterizer import GaussianRasterizerBatch
     cache = {}
 
@@ -168,10 +170,11 @@ def batch_renderer(settings_all: Sequence):
             cache[key] = GaussianRasterizerBatch([settings_all[c] for c in cams], track_densify=True)
         ras = cache[key]
         if "semantic_feature" in rv:  # label=None: every Gaussian's gradients kept (the G3 call's ones)
-            im, _radius, feat, _depth, _alpha = ras(**rv, label=None, feature_ready=feature_ready)
-            return (im, feat), ras.densify_stats
-        im, _radius, _depth = ras(**rv)  # G1 call (train.py:142)
-        return im, ras.densify_stats
+            im, _radius, feat, depth, _alpha = ras(**rv, label=None, feature_ready=feature_ready)
+            im = (im, feat)
+        else:
+            im, _radius, depth = ras(**rv)  # G1 call (train.py:142)
+        return (im, ras.densify_stats, depth) if with_depth else (im, ras.densify_stats)
 
     return render
 
@@ -189,7 +192,13 @@ class TimestepDriver:
     (default: batch_renderer(settings_all)).  `targets(t)` -> [n_cams, 3, H, W]
     images of timestep t, or only this rank's cameras' [C_rank, 3, H, W] with
     `targets_sharded=True` (a tuple of such tensors, e.g. images and feature
-    maps, when the render returns a tuple).
+    maps, when the render returns a tuple).  `depth_loss(depth, cams)` (optional)
+    maps the rank's depth planes [C, 1, H, W] and its camera indices to the SUM
+    of its cameras' depth losses, e.g. a closure over depth_loss.
+    depth_correlation_loss with the priors and the reference's weight 0.001
+    (dyn_train.py:256-265); it enters the loss divided by n_cams like the image
+    loss and needs a `render` that returns (images, stats, depth)
+    (batch_renderer(..., with_depth=True)).
 
     The optimizer step.  Two paths, the same arithmetic:
       * plain: ONE GradBucket all_reduce(SUM) of every gradient and the
@@ -235,7 +244,7 @@ class TimestepDriver:
                  rank: int = 0, world: int = 1, group=None,
                  image_loss: Callable = l1_image_loss, extra_loss: Optional[Callable] = None,
                  densify: Optional[Callable] = None, targets_sharded: bool = False,
-                 stat_scale: Optional[float] = None, sharded=None):
+                 stat_scale: Optional[float] = None, sharded=None, depth_loss: Optional[Callable] = None):
         self.params, self.variables, self.optimizer = params, variables, optimizer
         self.n_cams = n_cams
         self.stat_scale = float(n_cams if stat_scale is None else stat_scale)
@@ -244,6 +253,7 @@ class TimestepDriver:
         self.rank, self.world, self.group = rank, world, group
         self.render = render
         self.image_loss, self.extra_loss, self.densify = image_loss, extra_loss, densify
+        self.depth_loss = depth_loss
         dev = params["means3D"].device
         P = params["means3D"].shape[0]
         for k in STATS:
@@ -328,9 +338,13 @@ class TimestepDriver:
         stats = None
         if self.cams:
             if feature_ready is not None:
-                im, stats = self.render(rv, self.cams, feature_ready=feature_ready)
+                out = self.render(rv, self.cams, feature_ready=feature_ready)
             else:
-                im, stats = self.render(rv, self.cams)
+                out = self.render(rv, self.cams)
+            if self.depth_loss is not None and len(out) != 3:
+                raise ValueError("depth_loss needs a render that returns (images, stats, depth): "
+                                 "batch_renderer(settings_all, with_depth=True)")
+            im, stats = out[0], out[1]
             lead = targets[0] if isinstance(targets, (tuple, list)) else targets
             want = len(self.cams) if self.targets_sharded else self.n_cams
             if lead.shape[0] != want:
@@ -343,6 +357,8 @@ class TimestepDriver:
             else:
                 tg = targets[self.cams]
             loss = self.image_loss(im, tg) / self.n_cams
+            if self.depth_loss is not None:
+                loss = loss + self.depth_loss(out[2], self.cams) / self.n_cams
         if self.extra_loss is not None:
             le = self.extra_loss(self.params, self.variables, rv, t) / self.world
             loss = le if loss is None else loss + le
