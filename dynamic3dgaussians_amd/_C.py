@@ -18,6 +18,7 @@ from __future__ import annotations
 
 import ctypes
 import importlib.util
+import math
 import os
 import warnings
 
@@ -29,9 +30,11 @@ from ._lib import GsCamera, GsGaussians, check
 _default_compat = "reference"
 
 # Native fast path (csrc/gs_torch_binding.cpp, lib/_gs_native.so): the same
-# argument handling in C++ over the same C ABI, ~0.2 ms less host time per
-# camera than the ctypes code below, which stays the documented binding (and
-# serves P == 0, CPU-tensor errors, build variants and GS_NATIVE_BINDING=0).
+# argument handling in C++ over the same C ABI (forward_batch / backward_batch,
+# the counterparts of rasterize_gaussians_batch / _backward below), ~0.2 ms
+# less host time per camera than the ctypes code, which stays the documented
+# binding (and serves P == 0, CPU-tensor errors, build variants and
+# GS_NATIVE_BINDING=0).
 _native = None
 _native_tried = False
 
@@ -158,15 +161,20 @@ class _Inputs:
                            densify_accum=None, densify_denom=None, max_radius=None)
 
 
-def _camera(dev, background, viewmatrix, projmatrix, campos, c_x, c_y, tan_fovx, tan_fovy, W, H):
-    keep = [_dev(background, dev, "bg").reshape(-1), _dev(viewmatrix, dev, "viewmatrix").reshape(-1),
-            _dev(projmatrix, dev, "projmatrix").reshape(-1), _dev(campos, dev, "campos").reshape(-1)]
-    cam = GsCamera(viewmatrix=_ptr(keep[1]), projmatrix=_ptr(keep[2]), campos=_ptr(keep[3]),
-                   background=_ptr(keep[0]), c_x=float(c_x), c_y=float(c_y),
-                   tan_fovx=float(tan_fovx), tan_fovy=float(tan_fovy),
-                   image_width=int(W), image_height=int(H))
-    return cam, keep
+def _native_serves(nat, means3D) -> bool:
+    """The C++ fast path takes the call; P == 0 and the argument errors of
+    host tensors are answered by the ctypes code."""
+    return nat is not None and means3D.is_cuda and means3D.dim() == 2 and means3D.size(0) > 0
 
+
+def _user_width(t, dim, inp):
+    """An output of the compiled feature width cut back to the caller's."""
+    return t.narrow(dim, 0, inp.F_user) if inp.F_user != inp.F else t
+
+
+# A single camera is a batch of one: the two functions below wrap their
+# camera as one-element lists, call the batch code further down (the one place
+# the arguments are handled) and strip the leading camera dimension (views).
 
 def rasterize_gaussians(background, means3D, colors, semantic_feature, opacity, scales, rotations,
                         scale_modifier, cov3D_precomp, viewmatrix, projmatrix, c_x, c_y, tan_fovx,
@@ -177,65 +185,15 @@ def rasterize_gaussians(background, means3D, colors, semantic_feature, opacity, 
     Returns (num_rendered, color[3,H,W], feature_map[F,H,W], depth[1,H,W],
     alpha[1,H,W], radii[P] int32, geomBuffer, binningBuffer, imgBuffer).
     """
-    L_ = _lib.load()
-    cm = _compat_code(compat)
-    nat = _native_mod()
-    if nat is not None and means3D.is_cuda and means3D.dim() == 2 and means3D.size(0) > 0:
-        try:
-            return nat.forward(background, means3D, _opt(colors), _opt(semantic_feature), _opt(opacity),
-                               _opt(scales), _opt(rotations), float(scale_modifier), _opt(cov3D_precomp),
-                               viewmatrix, projmatrix, float(c_x), float(c_y), float(tan_fovx),
-                               float(tan_fovy), int(image_height), int(image_width), _opt(sh), int(degree),
-                               campos, bool(prefiltered), bool(debug), cm,
-                               _lib.stream(means3D.device))
-        except RuntimeError as ex:
-            raise _lib.GsplatError(str(ex)) from None
-    inp = _Inputs(means3D, colors, semantic_feature, opacity, scales, rotations, scale_modifier,
-                  cov3D_precomp, sh, degree)
-    dev, P = inp.device, inp.P
-    H, W = int(image_height), int(image_width)
-    f32 = dict(dtype=torch.float32, device=dev)
-    u8 = dict(dtype=torch.uint8, device=dev)
-    if P == 0:
-        return (0, torch.zeros(3, H, W, **f32), torch.zeros(inp.F_user, H, W, **f32),
-                torch.zeros(1, H, W, **f32), torch.zeros(1, H, W, **f32),
-                torch.zeros(0, dtype=torch.int32, device=dev), torch.empty(0, **u8),
-                torch.empty(0, **u8), torch.empty(0, **u8))
-    cam, keep = _camera(dev, background, viewmatrix, projmatrix, campos, c_x, c_y, tan_fovx,
-                        tan_fovy, W, H)
-    g = inp.struct()
-    out_color = torch.empty(3, H, W, **f32)
-    out_feature = torch.empty(inp.F, H, W, **f32)
-    out_depth = torch.empty(1, H, W, **f32)
-    # Q1: the reference never writes out_alpha (it stays 0; the kernel stores
-    # those zeros); "fixed" writes 1 - T.
-    out_alpha = torch.empty(1, H, W, **f32)
-    radii = torch.empty(P, dtype=torch.int32, device=dev)
-    geom = torch.empty(L_.gs_geom_buffer_bytes(P), **u8)
-    img = torch.empty(L_.gs_image_buffer_bytes(W, H), **u8)
-    stream = _lib.stream(dev)
-    L = ctypes.c_int64(0)
-    NI = ctypes.c_int64(0)
-    check(L_.gs_forward_plan(ctypes.byref(g), ctypes.byref(cam), int(bool(prefiltered)),
-                             int(bool(debug)), cm, geom.data_ptr(), img.data_ptr(), radii.data_ptr(),
-                             ctypes.byref(L), ctypes.byref(NI),
-                             stream), "rasterize_gaussians (preprocess)")
     # num_rendered is the reference's count (returned, like the reference);
     # the binned tile lists hold num_instances <= num_rendered entries
-    num_rendered = int(L.value)
-    num_instances = int(NI.value)
-    binning = torch.empty(L_.gs_binning_buffer_bytes(num_instances), **u8)
-    check(L_.gs_forward_render(ctypes.byref(g), ctypes.byref(cam), int(bool(debug)), cm,
-                               geom.data_ptr(), binning.data_ptr(), img.data_ptr(), num_instances,
-                               radii.data_ptr(), out_color.data_ptr(),
-                               out_feature.data_ptr() if inp.F else None, out_depth.data_ptr(),
-                               out_alpha.data_ptr(), stream), "rasterize_gaussians (render)")
-    del keep
-    feature_map = out_feature[:inp.F_user] if inp.F_user != inp.F else out_feature
-    return (num_rendered, out_color, feature_map, out_depth, out_alpha, radii, geom, binning, img)
-
-
-_BUFFER_ORDER = ("dmeans2D", "dcolors", "dsem", "dopacity", "dmeans3D", "dcov3D", "dsh", "dscales", "drot")
+    NR, color, fmap, depth, alpha, radii, geom, binning, img, NI = rasterize_gaussians_batch(
+        background, means3D, colors, semantic_feature, opacity, scales, rotations, scale_modifier,
+        cov3D_precomp, viewmatrix, projmatrix, [c_x], [c_y], [tan_fovx], [tan_fovy], image_height,
+        image_width, sh, degree, campos, prefiltered, debug, compat=compat)
+    if not NI[0]:
+        binning = binning[:0]  # no instances: the empty buffer this function has always returned
+    return (NR[0], color[0], fmap[0], depth[0], alpha[0], radii[0], geom, binning, img)
 
 
 def spatial_order(means3D: torch.Tensor) -> torch.Tensor:
@@ -255,12 +213,15 @@ def spatial_order(means3D: torch.Tensor) -> torch.Tensor:
     return order
 
 
-_NO_DEST = torch.empty(0)  # backward_batch's `out` entry: allocate this gradient
-
-
 def _buffer_shapes(P, F, M):
+    """The backward's nine gradients, in the order of its return tuple."""
     return dict(dmeans2D=(P, 3), dcolors=(P, 3), dsem=(P, F), dopacity=(P, 1), dmeans3D=(P, 3),
                 dcov3D=(P, 6), dsh=(P, M, 3), dscales=(P, 3), drot=(P, 4))
+
+
+_BUFFER_ORDER = tuple(_buffer_shapes(0, 0, 0))
+_BUFFER_NAMES = frozenset(_BUFFER_ORDER)
+_NO_DEST = torch.empty(0)  # the native backward's `out` entry: allocate this gradient
 
 
 def backward_buffers(P, F, M, device, flat=False):
@@ -274,9 +235,7 @@ def backward_buffers(P, F, M, device, flat=False):
         return {k: torch.empty(*shape, dtype=torch.float32, device=device) for k, shape in shapes.items()}
     offs, o = {}, 0
     for k, shape in shapes.items():
-        n = 1
-        for d in shape:
-            n *= d
+        n = math.prod(shape)
         offs[k] = (o, n, shape)
         o += (n + 63) // 64 * 64
     buf = torch.empty(max(o, 1), dtype=torch.float32, device=device)
@@ -317,85 +276,11 @@ def rasterize_gaussians_backward(background, means3D, radii, colors, semantic_fe
     statistics (external.py:136-140, train.py:288-290; gsplat_hip.h
     gs_gaussians.densify_accum), written or, with `accumulate`, added.
     """
-    L_ = _lib.load()
-    cm = _compat_code(compat)
-    nat = _native_mod()
-    if nat is not None and means3D.is_cuda and means3D.dim() == 2 and means3D.size(0) > 0:
-        if accumulate and out is None:
-            raise ValueError("accumulate=True needs the caller's gradient buffers (out=...)")
-        try:
-            return nat.backward(background, means3D, radii, _opt(colors), _opt(semantic_feature),
-                                _opt(scales), _opt(rotations), float(scale_modifier), _opt(cov3D_precomp),
-                                viewmatrix, projmatrix, float(c_x), float(c_y), float(tan_fovx),
-                                float(tan_fovy), _opt(dL_dout_color), _opt(dL_dout_feature),
-                                _opt(dL_dout_depth), _opt(dL_dout_alpha), _opt(sh), int(degree), campos,
-                                geomBuffer, int(R), _opt(binningBuffer), imageBuffer, alphas, bool(debug), cm,
-                                _opt(grad_mask), None if out is None else [out[k] for k in _BUFFER_ORDER],
-                                bool(accumulate), None if densify is None else list(densify),
-                                _lib.stream(means3D.device))
-        except RuntimeError as ex:
-            raise _lib.GsplatError(str(ex)) from None
-    inp = _Inputs(means3D, colors, semantic_feature, None, scales, rotations, scale_modifier,
-                  cov3D_precomp, sh, degree)
-    dev, P = inp.device, inp.P
-    # rasterize_points.cu:160-161 takes H, W from dL_dout_color; an absent
-    # (None / empty) upstream gradient counts as zeros, sized from the alpha image
-    img_ref = dL_dout_color if _present(dL_dout_color) else alphas
-    H, W = img_ref.size(-2), img_ref.size(-1)
-    f32 = dict(dtype=torch.float32, device=dev)
-    if P == 0:
-        z = lambda *s: torch.zeros(*s, **f32)  # noqa: E731
-        return (z(0, 3), z(0, 3), z(0, inp.F_user), z(0, 1), z(0, 3), z(0, 6), z(0, inp.M, 3),
-                z(0, 3), z(0, 4))
-    cam, keep = _camera(dev, background, viewmatrix, projmatrix, campos, c_x, c_y, tan_fovx,
-                        tan_fovy, W, H)
-    g = inp.struct()
-    if grad_mask is not None:
-        gm = grad_mask.to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
-        if gm.numel() != P:
-            raise RuntimeError(f"grad_mask must have {P} elements, got {gm.numel()}")
-        g.grad_mask = gm.data_ptr()
-    dLc = _dev(dL_dout_color, dev, "dL_dout_color") if _present(dL_dout_color) else None
-    dLd = _dev(dL_dout_depth, dev, "dL_dout_depth") if _present(dL_dout_depth) else None
-    dLa = _dev(dL_dout_alpha, dev, "dL_dout_alpha") if _present(dL_dout_alpha) else None
-    alphas_c = _dev(alphas, dev, "alpha")
-    dLf = None
-    if inp.F and _present(dL_dout_feature):
-        dLf = _dev(dL_dout_feature, dev, "dL_dout_feature").reshape(-1, H, W)
-        if dLf.size(0) < inp.F:
-            dLf = torch.cat([dLf, torch.zeros(inp.F - dLf.size(0), H, W, **f32)]).contiguous()
-    radii_c = radii.to(device=dev, dtype=torch.int32).contiguous()
-    if out is None:
-        if accumulate:
-            raise ValueError("accumulate=True needs the caller's gradient buffers (out=...)")
-        out = backward_buffers(P, inp.F, inp.M, dev)
-    else:
-        for k, shape in _buffer_shapes(P, inp.F, inp.M).items():
-            t = out[k]
-            if (tuple(t.shape) != shape or t.dtype != torch.float32 or t.device != dev
-                    or not t.is_contiguous()):
-                raise RuntimeError(f"gradient buffer {k} must be a contiguous fp32 {shape} tensor on {dev}")
-        if accumulate:
-            g.flags = _lib.GS_FLAG_ACCUMULATE
-    if densify is not None:
-        for t in densify:
-            if tuple(t.shape) != (P,) or t.dtype != torch.float32 or t.device != dev or not t.is_contiguous():
-                raise RuntimeError(f"densify statistics must be contiguous fp32 ({P},) tensors on {dev}")
-        g.densify_accum, g.densify_denom, g.max_radius = (t.data_ptr() for t in densify)
-    scratch = torch.empty(L_.gs_backward_scratch_bytes(P, inp.F), dtype=torch.uint8, device=dev)
-    stream = _lib.stream(dev)
-    p = lambda t: t.data_ptr() if (t is not None and t.numel()) else None  # noqa: E731
-    check(L_.gs_backward(ctypes.byref(g), ctypes.byref(cam), radii_c.data_ptr(), int(bool(debug)), cm,
-                         geomBuffer.data_ptr(), p(binningBuffer), imageBuffer.data_ptr(), int(R),
-                         alphas_c.data_ptr(), p(dLc), p(dLf), p(dLd), p(dLa),
-                         scratch.data_ptr(), out["dmeans2D"].data_ptr(), out["dcolors"].data_ptr(),
-                         p(out["dsem"]), out["dopacity"].data_ptr(), out["dmeans3D"].data_ptr(),
-                         out["dcov3D"].data_ptr(), p(out["dsh"]), out["dscales"].data_ptr(),
-                         out["drot"].data_ptr(), stream), "rasterize_gaussians_backward")
-    del keep
-    dsem = out["dsem"][:, :inp.F_user] if inp.F_user != inp.F else out["dsem"]
-    return (out["dmeans2D"], out["dcolors"], dsem, out["dopacity"], out["dmeans3D"],
-            out["dcov3D"], out["dsh"], out["dscales"], out["drot"])
+    return _backward(background, means3D, radii.unsqueeze(0), colors, semantic_feature, scales, rotations,
+                     scale_modifier, cov3D_precomp, viewmatrix, projmatrix, [c_x], [c_y], [tan_fovx], [tan_fovy],
+                     dL_dout_color, dL_dout_feature, dL_dout_depth, dL_dout_alpha, sh, degree, campos, geomBuffer,
+                     [R], binningBuffer, imageBuffer, alphas, debug, compat=compat, grad_mask=grad_mask,
+                     densify=densify, out=out, exact_out=True, accumulate=accumulate)
 
 
 def binned_instances(imageBuffer, image_height, image_width) -> int:
@@ -432,6 +317,9 @@ def mark_visible(means3D, viewmatrix, projmatrix):
 # ---------------------------------------------------------------------------
 # Camera batches (include/gsplat_hip.h gs_*_batch; no reference analogue): the
 # C cameras of one multi-camera step rendered with one launch per stage.
+# rasterize_gaussians_batch and _backward are the forward and backward bodies
+# of every call, the single-camera functions above included (C = 1, where the
+# batch entry points run exactly what the single-camera ones run).
 
 def _camera_batch(dev, background, viewmatrices, projmatrices, campos, c_x, c_y, tan_fovx, tan_fovy, W, H,
                   windows=None):
@@ -454,7 +342,7 @@ def _camera_batch(dev, background, viewmatrices, projmatrices, campos, c_x, c_y,
                            image_width=int(W), image_height=int(H))
         if windows is not None and windows[c] is not None:
             cams[c].tile_x0, cams[c].tile_y0, cams[c].tile_x1, cams[c].tile_y1 = (int(v) for v in windows[c])
-    return cams, C, [view, proj, cpos, bg]
+    return cams, [view, proj, cpos, bg]
 
 
 def _event_handle(ev) -> int:
@@ -462,7 +350,7 @@ def _event_handle(ev) -> int:
     return 0 if ev is None else int(ev.cuda_event)
 
 
-def _windows_arg(windows, C):
+def _windows_arg(windows):
     """Tile windows as the native binding takes them: C x [x0, y0, x1, y1]
     (all 0 = the whole image), or an empty list for none."""
     if windows is None:
@@ -560,16 +448,16 @@ def rasterize_gaussians_batch(background, means3D, colors, semantic_feature, opa
             torch.cuda.current_stream(means3D.device).wait_event(feature_ready)
             feature_ready = None
     nat = _native_mod()
-    if nat is not None and means3D.is_cuda and means3D.dim() == 2 and means3D.size(0) > 0:
-        C_ = len(c_x)
-        cap = plan_state.next_capacity(C_) if sync_free else []
+    C = len(c_x)
+    if _native_serves(nat, means3D):
+        cap = plan_state.next_capacity(C) if sync_free else []
         try:
             out = nat.forward_batch(background, means3D, _opt(colors), _opt(semantic_feature), _opt(opacity),
                                     _opt(scales), _opt(rotations), float(scale_modifier), _opt(cov3D_precomp),
                                     viewmatrices, projmatrices, [float(x) for x in c_x], [float(x) for x in c_y],
                                     [float(x) for x in tan_fovx], [float(x) for x in tan_fovy], int(image_height),
                                     int(image_width), _opt(sh), int(degree), campos, bool(prefiltered),
-                                    bool(debug), cm, bool(activate), _windows_arg(windows, C_),
+                                    bool(debug), cm, bool(activate), _windows_arg(windows),
                                     _event_handle(feature_ready), cap,
                                     plan_state.hint if sync_free else [], _opt(walk_order), _opt(zero_fill),
                                     _lib.stream(means3D.device))
@@ -584,15 +472,15 @@ def rasterize_gaussians_batch(background, means3D, colors, semantic_feature, opa
                   cov3D_precomp, sh, degree)
     dev, P = inp.device, inp.P
     H, W = int(image_height), int(image_width)
-    cams, C, keep = _camera_batch(dev, background, viewmatrices, projmatrices, campos, c_x, c_y, tan_fovx,
-                                  tan_fovy, W, H, windows)
     f32 = dict(dtype=torch.float32, device=dev)
     u8 = dict(dtype=torch.uint8, device=dev)
-    if P == 0:
+    if P == 0:  # answered before any camera argument is looked at
         return ([0] * C, torch.zeros(C, 3, H, W, **f32), torch.zeros(C, inp.F_user, H, W, **f32),
                 torch.zeros(C, 1, H, W, **f32), torch.zeros(C, 1, H, W, **f32),
                 torch.zeros(C, 0, dtype=torch.int32, device=dev), torch.empty(0, **u8), torch.empty(0, **u8),
                 torch.empty(0, **u8), [0] * C)
+    cams, keep = _camera_batch(dev, background, viewmatrices, projmatrices, campos, c_x, c_y, tan_fovx,
+                               tan_fovy, W, H, windows)
     g = inp.struct(_lib.GS_FLAG_ACTIVATE if activate else 0)
     g.feature_ready = _event_handle(feature_ready) or None
     if walk_order is not None:
@@ -608,6 +496,8 @@ def rasterize_gaussians_batch(background, means3D, colors, semantic_feature, opa
     out_color = torch.empty(C, 3, H, W, **f32)
     out_feature = torch.empty(C, inp.F, H, W, **f32)
     out_depth = torch.empty(C, 1, H, W, **f32)
+    # Q1: the reference never writes out_alpha (it stays 0; the kernel stores
+    # those zeros); "fixed" writes 1 - T.
     out_alpha = torch.empty(C, 1, H, W, **f32)
     radii = torch.empty(C, P, dtype=torch.int32, device=dev)
     geom = torch.empty(L_.gs_batch_geom_buffer_bytes(P, C), **u8)
@@ -645,8 +535,8 @@ def rasterize_gaussians_batch(background, means3D, colors, semantic_feature, opa
         plan_state.update(list(NI), [hint.valid, hint.p1, hint.q1, hint.p2, hint.max_len, hint.total], fitted,
                           first=not any(cap_list))
     del keep
-    feature_map = out_feature[:, :inp.F_user] if inp.F_user != inp.F else out_feature
-    return (list(NR), out_color, feature_map, out_depth, out_alpha, radii, geom, binning, img, layout)
+    return (list(NR), out_color, _user_width(out_feature, 1, inp), out_depth, out_alpha, radii, geom, binning, img,
+            layout)
 
 
 def rasterize_gaussians_batch_backward(background, means3D, radii, colors, semantic_feature, scales,
@@ -673,53 +563,90 @@ def rasterize_gaussians_batch_backward(background, means3D, radii, colors, seman
     backward's scratch (gs_batch_backward_scratch_bytes) kept from the
     forward, `scratch_zeroed`: the forward's blend zeroed it
     (rasterize_gaussians_batch zero_fill; GS_FLAG_SCRATCH_ZEROED)."""
+    return _backward(background, means3D, radii, colors, semantic_feature, scales, rotations, scale_modifier,
+                     cov3D_precomp, viewmatrices, projmatrices, c_x, c_y, tan_fovx, tan_fovy, dL_dout_color,
+                     dL_dout_feature, dL_dout_depth, dL_dout_alpha, sh, degree, campos, geomBuffer, num_instances,
+                     binningBuffer, imageBuffer, alphas, debug, compat=compat, grad_mask=grad_mask, densify=densify,
+                     opacity=opacity, activate=activate, windows=windows, out=out, scratch=scratch,
+                     scratch_zeroed=scratch_zeroed)
+
+
+def _gradient_outputs(out, exact, P, F, M, dev):
+    """The backward's nine gradient tensors by name: fresh ones, or the
+    caller's `out` -- with `exact` in backward_buffers' shapes (the
+    GradientSink contract), else matched by element count and viewed in those
+    shapes (a gradient bucket's flat views)."""
+    bufs = {}
+    for k, shape in _buffer_shapes(P, F, M).items():
+        t = None if out is None else out.get(k)
+        if t is None:
+            bufs[k] = torch.empty(*shape, dtype=torch.float32, device=dev)
+            continue
+        n = math.prod(shape)
+        fits = tuple(t.shape) == shape if exact else t.numel() == n
+        if not fits or t.dtype != torch.float32 or t.device != dev or not t.is_contiguous():
+            want = f"{shape} tensor" if exact else f"tensor of {n} elements"
+            raise RuntimeError(f"gradient buffer {k} must be a contiguous fp32 {want} on {dev}")
+        bufs[k] = t.view(shape)
+    return bufs
+
+
+def _backward(background, means3D, radii, colors, semantic_feature, scales, rotations, scale_modifier,
+              cov3D_precomp, viewmatrices, projmatrices, c_x, c_y, tan_fovx, tan_fovy, dL_dout_color,
+              dL_dout_feature, dL_dout_depth, dL_dout_alpha, sh, degree, campos, geomBuffer, num_instances,
+              binningBuffer, imageBuffer, alphas, debug, *, compat, grad_mask, densify, opacity=None,
+              activate=False, windows=None, out=None, exact_out=False, accumulate=False, scratch=None,
+              scratch_zeroed=False):
+    """The one backward body, for C = len(c_x) cameras (gs_backward_batch; at
+    C = 1 what the single-camera entry point runs).  `exact_out`: `out` holds every gradient
+    name in its exact shape (else any subset, by element count);
+    `accumulate`: the gradients are ADDED to `out` (GS_FLAG_ACCUMULATE)."""
     L_ = _lib.load()
     cm = _compat_code(compat)
     if activate and not _present(opacity):
         raise RuntimeError("activate=True needs the raw opacities")
-    if out:
-        unknown = set(out) - set(_buffer_shapes(0, 0, 0))
-        if unknown:
-            raise RuntimeError(f"out: unknown gradient names {sorted(unknown)}")
+    if accumulate and out is None:
+        raise ValueError("accumulate=True needs the caller's gradient buffers (out=...)")
+    if out is not None:
+        odd = _BUFFER_NAMES - out.keys() if exact_out else out.keys() - _BUFFER_NAMES
+        if odd:
+            raise RuntimeError(f"out: {'missing' if exact_out else 'unknown'} gradient names {sorted(odd)}")
     nat = _native_mod()
-    if nat is not None and means3D.is_cuda and means3D.dim() == 2 and means3D.size(0) > 0:
+    C = len(c_x)
+    if _native_serves(nat, means3D):
         try:
-            return nat.backward_batch(background, means3D, radii, _opt(colors), _opt(semantic_feature),
-                                      _opt(scales), _opt(rotations), float(scale_modifier), _opt(cov3D_precomp),
-                                      viewmatrices, projmatrices, [float(x) for x in c_x],
-                                      [float(x) for x in c_y], [float(x) for x in tan_fovx],
-                                      [float(x) for x in tan_fovy], _opt(dL_dout_color), _opt(dL_dout_feature),
-                                      _opt(dL_dout_depth), _opt(dL_dout_alpha), _opt(sh), int(degree), campos,
-                                      geomBuffer, [int(x) for x in num_instances], _opt(binningBuffer),
-                                      imageBuffer, alphas, bool(debug), cm, _opt(grad_mask),
-                                      None if densify is None else list(densify), _opt(opacity), bool(activate),
-                                      _windows_arg(windows, len(c_x)),
-                                      [out.get(k, _NO_DEST) for k in _buffer_shapes(0, 0, 0)] if out else [],
-                                      _opt(scratch), bool(scratch_zeroed),
-                                      _lib.stream(means3D.device))
+            return tuple(nat.backward_batch(
+                background, means3D, radii, _opt(colors), _opt(semantic_feature), _opt(scales), _opt(rotations),
+                float(scale_modifier), _opt(cov3D_precomp), viewmatrices, projmatrices, [float(x) for x in c_x],
+                [float(x) for x in c_y], [float(x) for x in tan_fovx], [float(x) for x in tan_fovy],
+                _opt(dL_dout_color), _opt(dL_dout_feature), _opt(dL_dout_depth), _opt(dL_dout_alpha), _opt(sh),
+                int(degree), campos, geomBuffer, [int(x) for x in num_instances], _opt(binningBuffer), imageBuffer,
+                alphas, bool(debug), cm, _opt(grad_mask), None if densify is None else list(densify),
+                _opt(opacity), bool(activate), _windows_arg(windows),
+                [out.get(k, _NO_DEST) for k in _BUFFER_ORDER] if out else [], bool(exact_out), bool(accumulate),
+                _opt(scratch), bool(scratch_zeroed), _lib.stream(means3D.device)))
         except RuntimeError as ex:
             raise _lib.GsplatError(str(ex)) from None
     inp = _Inputs(means3D, colors, semantic_feature, opacity if activate else None, scales, rotations,
                   scale_modifier, cov3D_precomp, sh, degree)
     dev, P = inp.device, inp.P
-    C = len(c_x)
+    f32 = dict(dtype=torch.float32, device=dev)
+    if P == 0:  # answered before any camera argument is looked at
+        return tuple(torch.zeros(*shape, **f32) for shape in _buffer_shapes(0, inp.F_user, inp.M).values())
+    # rasterize_points.cu:160-161 takes H, W from dL_dout_color; an absent
+    # (None / empty) upstream gradient counts as zeros, sized from the alpha image
     img_ref = dL_dout_color if _present(dL_dout_color) else alphas
     H, W = img_ref.size(-2), img_ref.size(-1)
-    f32 = dict(dtype=torch.float32, device=dev)
-    if P == 0:
-        z = lambda *s: torch.zeros(*s, **f32)  # noqa: E731
-        return (z(0, 3), z(0, 3), z(0, inp.F_user), z(0, 1), z(0, 3), z(0, 6), z(0, inp.M, 3),
-                z(0, 3), z(0, 4))
-    cams, C, keep = _camera_batch(dev, background, viewmatrices, projmatrices, campos, c_x, c_y, tan_fovx,
-                                  tan_fovy, W, H, windows)
-    g = inp.struct(_lib.GS_FLAG_ACTIVATE if activate else 0)
+    cams, keep = _camera_batch(dev, background, viewmatrices, projmatrices, campos, c_x, c_y, tan_fovx,
+                               tan_fovy, W, H, windows)
+    g = inp.struct((_lib.GS_FLAG_ACTIVATE if activate else 0) | (_lib.GS_FLAG_ACCUMULATE if accumulate else 0))
     if grad_mask is not None:
         gm = grad_mask.to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
         if gm.numel() != P:
             raise RuntimeError(f"grad_mask must have {P} elements, got {gm.numel()}")
         g.grad_mask = gm.data_ptr()
 
-    def img(t, ch, name):
+    def img(t, ch, name):  # [C, ch, H, W] of an upstream gradient (channels zero-padded), or None
         if not _present(t):
             return None
         t = _dev(t, dev, name).reshape(C, -1, H, W)
@@ -734,13 +661,7 @@ def rasterize_gaussians_batch_backward(background, means3D, radii, colors, seman
     radii_c = radii.to(device=dev, dtype=torch.int32).contiguous()
     if tuple(radii_c.shape) != (C, P):
         raise RuntimeError(f"radii must be [C={C}, P={P}]")
-    dest = out or {}
-    out = backward_buffers(P, inp.F, inp.M, dev)
-    for k, t in dest.items():
-        want = out[k]
-        if t.dtype != torch.float32 or t.device != dev or not t.is_contiguous() or t.numel() != want.numel():
-            raise RuntimeError(f"out['{k}'] must be a contiguous fp32 tensor of {want.numel()} elements on {dev}")
-        out[k] = t.view(want.shape)
+    out = _gradient_outputs(out, exact_out, P, inp.F, inp.M, dev)
     if densify is not None:
         for t in densify:
             if tuple(t.shape) != (P,) or t.dtype != torch.float32 or t.device != dev or not t.is_contiguous():
@@ -760,11 +681,9 @@ def rasterize_gaussians_batch_backward(background, means3D, radii, colors, seman
     check(L_.gs_backward_batch(ctypes.byref(g), cams, C, radii_c.data_ptr(), int(bool(debug)), cm,
                                geomBuffer.data_ptr(), p(binningBuffer), imageBuffer.data_ptr(), NI,
                                alphas_c.data_ptr(), p(dLc), p(dLf), p(dLd), p(dLa), scratch.data_ptr(),
-                               out["dmeans2D"].data_ptr(), out["dcolors"].data_ptr(), p(out["dsem"]),
-                               out["dopacity"].data_ptr(), out["dmeans3D"].data_ptr(), out["dcov3D"].data_ptr(),
-                               p(out["dsh"]), out["dscales"].data_ptr(), out["drot"].data_ptr(), stream),
-          "rasterize_gaussians_batch_backward")
+                               *(p(out[k]) if k in ("dsem", "dsh") else out[k].data_ptr() for k in _BUFFER_ORDER),
+                               stream), "rasterize_gaussians_batch_backward")
     del keep
-    dsem = out["dsem"][:, :inp.F_user] if inp.F_user != inp.F else out["dsem"]
-    return (out["dmeans2D"], out["dcolors"], dsem, out["dopacity"], out["dmeans3D"],
-            out["dcov3D"], out["dsh"], out["dscales"], out["drot"])
+    out["dsem"] = _user_width(out["dsem"], 1, inp)
+    return tuple(out[k] for k in _BUFFER_ORDER)
+

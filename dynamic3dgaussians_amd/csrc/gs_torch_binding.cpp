@@ -100,145 +100,16 @@ struct Inputs {
   }
 };
 
-struct Camera {
-  Tensor keep[4];
-  gs_camera cam{};
-  Camera(const at::Device& dev, const Tensor& bg, const Tensor& view, const Tensor& proj, const Tensor& campos,
-         double c_x, double c_y, double tanx, double tany, int64_t W, int64_t H) {
-    keep[0] = dev_f32(bg, dev, "bg").reshape({-1});
-    keep[1] = dev_f32(view, dev, "viewmatrix").reshape({-1});
-    keep[2] = dev_f32(proj, dev, "projmatrix").reshape({-1});
-    keep[3] = dev_f32(campos, dev, "campos").reshape({-1});
-    cam.background = keep[0].data_ptr<float>();
-    cam.viewmatrix = keep[1].data_ptr<float>();
-    cam.projmatrix = keep[2].data_ptr<float>();
-    cam.campos = keep[3].data_ptr<float>();
-    cam.c_x = (float)c_x;
-    cam.c_y = (float)c_y;
-    cam.tan_fovx = (float)tanx;
-    cam.tan_fovy = (float)tany;
-    cam.image_width = (int32_t)W;
-    cam.image_height = (int32_t)H;
-  }
-};
-
 void* nz(const Tensor& t) { return (t.defined() && t.numel()) ? t.data_ptr() : nullptr; }
 
-// RasterizeGaussiansCUDA (DGR/rasterize_points.cu:35-126), positional order of
-// _C.rasterize_gaussians + compat code + stream handle.  P > 0 (the Python
-// layer answers P == 0).
-std::tuple<int64_t, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> forward(
-    const Tensor& bg, const Tensor& means3D, const OptT& colors, const OptT& sem, const OptT& opacity,
-    const OptT& scales, const OptT& rotations, double scale_modifier, const OptT& cov3D, const Tensor& view,
-    const Tensor& proj, double c_x, double c_y, double tanx, double tany, int64_t H, int64_t W, const OptT& sh,
-    int64_t degree, const Tensor& campos, bool prefiltered, bool debug, int64_t compat, int64_t stream) {
-  Inputs in(means3D, colors, sem, opacity, scales, rotations, scale_modifier, cov3D, sh, degree);
-  Camera c(in.dev, bg, view, proj, campos, c_x, c_y, tanx, tany, W, H);
-  const auto f32 = at::TensorOptions().dtype(at::kFloat).device(in.dev);
-  const auto u8 = at::TensorOptions().dtype(at::kByte).device(in.dev);
-  Tensor out_color = at::empty({3, H, W}, f32);
-  Tensor out_feature = at::empty({in.F, H, W}, f32);
-  Tensor out_depth = at::empty({1, H, W}, f32);
-  Tensor out_alpha = at::empty({1, H, W}, f32);
-  Tensor radii = at::empty({in.P}, f32.dtype(at::kInt));
-  Tensor geom = at::empty({(int64_t)gs_geom_buffer_bytes(in.P)}, u8);
-  Tensor img = at::empty({(int64_t)gs_image_buffer_bytes((int32_t)W, (int32_t)H)}, u8);
-  int64_t L = 0, NI = 0;
-  gs_stream_t s = reinterpret_cast<gs_stream_t>(stream);
-  check(gs_forward_plan(&in.g, &c.cam, prefiltered ? 1 : 0, debug ? 1 : 0, (int)compat, geom.data_ptr(),
-                        img.data_ptr(), radii.data_ptr<int32_t>(), &L, &NI, s),
-        "rasterize_gaussians (preprocess)");
-  Tensor binning = at::empty({(int64_t)gs_binning_buffer_bytes(NI)}, u8);
-  check(gs_forward_render(&in.g, &c.cam, debug ? 1 : 0, (int)compat, geom.data_ptr(), binning.data_ptr(),
-                          img.data_ptr(), NI, radii.data_ptr<int32_t>(), out_color.data_ptr<float>(),
-                          in.F ? out_feature.data_ptr<float>() : nullptr, out_depth.data_ptr<float>(),
-                          out_alpha.data_ptr<float>(), s),
-        "rasterize_gaussians (render)");
-  Tensor feature_map = in.F_user != in.F ? out_feature.narrow(0, 0, in.F_user) : out_feature;
-  return {L, out_color, feature_map, out_depth, out_alpha, radii, geom, binning, img};
-}
+// One forward and one backward body over the gs_*_batch entry points, for any
+// number of cameras: the C++ counterpart of _C.rasterize_gaussians_batch and
+// _C._backward.  A single camera (_C.rasterize_gaussians / _backward) is a
+// batch of one, wrapped and unwrapped in Python.  The forward's one host
+// round trip (the plan header) sits between the two ABI calls, so the host
+// work around it is on the step's critical path.
 
-// RasterizeGaussiansBackwardCUDA (DGR/rasterize_points.cu:128-225), positional
-// order of _C.rasterize_gaussians_backward + compat code, optional label mask,
-// optional caller-owned buffers (9, in the output order) with the accumulate
-// flag, optional densification statistics (accum, denom, max_radius), and the
-// stream handle.
-std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> backward(
-    const Tensor& bg, const Tensor& means3D, const Tensor& radii, const OptT& colors, const OptT& sem,
-    const OptT& scales, const OptT& rotations, double scale_modifier, const OptT& cov3D, const Tensor& view,
-    const Tensor& proj, double c_x, double c_y, double tanx, double tany, const OptT& dL_color,
-    const OptT& dL_feature, const OptT& dL_depth, const OptT& dL_alpha, const OptT& sh, int64_t degree,
-    const Tensor& campos, const Tensor& geom, int64_t R, const OptT& binning, const Tensor& img,
-    const Tensor& alphas, bool debug, int64_t compat, const OptT& grad_mask, c10::optional<std::vector<Tensor>> out,
-    bool accumulate, c10::optional<std::vector<Tensor>> densify, int64_t stream) {
-  Inputs in(means3D, colors, sem, c10::nullopt, scales, rotations, scale_modifier, cov3D, sh, degree);
-  const Tensor& img_ref = present(dL_color) ? *dL_color : alphas;
-  const int64_t H = img_ref.size(-2), W = img_ref.size(-1);
-  Camera c(in.dev, bg, view, proj, campos, c_x, c_y, tanx, tany, W, H);
-  const auto f32 = at::TensorOptions().dtype(at::kFloat).device(in.dev);
-  const int64_t P = in.P;
-  Tensor gm;
-  if (grad_mask.has_value() && grad_mask->defined()) {
-    gm = grad_mask->to(in.dev, at::kFloat).reshape({-1}).contiguous();
-    if (gm.numel() != P) throw std::runtime_error("grad_mask must have P elements");
-    in.g.grad_mask = gm.data_ptr<float>();
-  }
-  Tensor dLc = present(dL_color) ? dev_f32(*dL_color, in.dev, "dL_dout_color") : Tensor();
-  Tensor dLd = present(dL_depth) ? dev_f32(*dL_depth, in.dev, "dL_dout_depth") : Tensor();
-  Tensor dLa = present(dL_alpha) ? dev_f32(*dL_alpha, in.dev, "dL_dout_alpha") : Tensor();
-  Tensor alphas_c = dev_f32(alphas, in.dev, "alpha");
-  Tensor dLf;
-  if (in.F && present(dL_feature)) {
-    dLf = dev_f32(*dL_feature, in.dev, "dL_dout_feature").reshape({-1, H, W});
-    if (dLf.size(0) < in.F) dLf = at::cat({dLf, at::zeros({in.F - dLf.size(0), H, W}, f32)}).contiguous();
-  }
-  Tensor radii_c = radii.to(in.dev, at::kInt).contiguous();
-  const std::vector<std::vector<int64_t>> shapes = {{P, 3}, {P, 3}, {P, in.F}, {P, 1}, {P, 3},
-                                                    {P, 6}, {P, in.M, 3}, {P, 3}, {P, 4}};
-  std::vector<Tensor> o;
-  if (out.has_value()) {
-    o = *out;
-    if (o.size() != 9) throw std::runtime_error("out must hold the 9 gradient buffers");
-    for (int i = 0; i < 9; ++i)
-      if (o[i].sizes() != at::IntArrayRef(shapes[i]) || o[i].scalar_type() != at::kFloat || o[i].device() != in.dev ||
-          !o[i].is_contiguous())
-        throw std::runtime_error("gradient buffer " + std::to_string(i) + " has the wrong shape/dtype/device");
-    if (accumulate) in.g.flags = GS_FLAG_ACCUMULATE;
-  } else {
-    if (accumulate) throw std::runtime_error("accumulate needs the caller's gradient buffers");
-    for (int i = 0; i < 9; ++i) o.push_back(at::empty(shapes[i], f32));
-  }
-  if (densify.has_value()) {
-    const auto& d = *densify;
-    if (d.size() != 3) throw std::runtime_error("densify must hold (accum, denom, max_radius)");
-    for (const auto& t : d)
-      if (t.dim() != 1 || t.size(0) != P || t.scalar_type() != at::kFloat || t.device() != in.dev || !t.is_contiguous())
-        throw std::runtime_error("densify statistics must be contiguous fp32 (P,) tensors on the device");
-    in.g.densify_accum = d[0].data_ptr<float>();
-    in.g.densify_denom = d[1].data_ptr<float>();
-    in.g.max_radius = d[2].data_ptr<float>();
-  }
-  Tensor scratch = at::empty({(int64_t)gs_backward_scratch_bytes(P, (int32_t)in.F)},
-                             f32.dtype(at::kByte));
-  const Tensor bin = binning.has_value() ? *binning : Tensor();
-  check(gs_backward(&in.g, &c.cam, radii_c.data_ptr<int32_t>(), debug ? 1 : 0, (int)compat, geom.data_ptr(),
-                    nz(bin), img.data_ptr(), R, alphas_c.data_ptr<float>(),
-                    dLc.defined() ? dLc.data_ptr<float>() : nullptr, dLf.defined() ? dLf.data_ptr<float>() : nullptr,
-                    dLd.defined() ? dLd.data_ptr<float>() : nullptr, dLa.defined() ? dLa.data_ptr<float>() : nullptr,
-                    scratch.data_ptr(), o[0].data_ptr<float>(), o[1].data_ptr<float>(),
-                    static_cast<float*>(nz(o[2])), o[3].data_ptr<float>(), o[4].data_ptr<float>(),
-                    o[5].data_ptr<float>(), static_cast<float*>(nz(o[6])), o[7].data_ptr<float>(),
-                    o[8].data_ptr<float>(), reinterpret_cast<gs_stream_t>(stream)),
-        "rasterize_gaussians_backward");
-  Tensor dsem = in.F_user != in.F ? o[2].narrow(1, 0, in.F_user) : o[2];
-  return {o[0], o[1], dsem, o[3], o[4], o[5], o[6], o[7], o[8]};
-}
-
-// ---- camera batches (gs_*_batch): the C++ counterpart of
-// _C.rasterize_gaussians_batch / rasterize_gaussians_batch_backward.  The
-// forward's one host round trip (the plan header) sits between the two ABI
-// calls, so the host work around it is on the step's critical path.
-
+// The C cameras of a call; the ABI checks that 1 <= C <= its camera limit.
 struct Cameras {
   Tensor view, proj, cpos, bg;
   std::vector<gs_camera> cams;
@@ -246,7 +117,7 @@ struct Cameras {
           const std::vector<double>& cx, const std::vector<double>& cy, const std::vector<double>& tx,
           const std::vector<double>& ty, int64_t W, int64_t H, const std::vector<std::vector<int64_t>>& windows) {
     const int64_t C = (int64_t)cx.size();
-    if (C < 1 || C > 64) throw std::runtime_error("camera batch size " + std::to_string(C) + " outside 1..64");
+    if (C < 1) throw std::runtime_error("camera batch size 0: a call takes at least one camera");
     if ((int64_t)cy.size() != C || (int64_t)tx.size() != C || (int64_t)ty.size() != C)
       throw std::runtime_error("per-camera scalars must all have C entries");
     view = dev_f32(views, dev, "viewmatrices").reshape({C, 16}).contiguous();
@@ -382,7 +253,60 @@ Tensor batch_image(const OptT& t, int64_t C, int64_t ch, int64_t H, int64_t W, c
   return u.contiguous();
 }
 
-std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor> backward_batch(
+void set_grad_mask(Inputs& in, const OptT& grad_mask, Tensor& keep) {
+  if (!grad_mask.has_value() || !grad_mask->defined()) return;
+  keep = grad_mask->to(in.dev, at::kFloat).reshape({-1}).contiguous();
+  if (keep.numel() != in.P)
+    throw std::runtime_error("grad_mask must have " + std::to_string(in.P) + " elements, got " +
+                             std::to_string(keep.numel()));
+  in.g.grad_mask = keep.data_ptr<float>();
+}
+
+// (accum, denom, max_radius): this call's densification statistics
+void set_densify(Inputs& in, const c10::optional<std::vector<Tensor>>& densify) {
+  if (!densify.has_value()) return;
+  const auto& d = *densify;
+  if (d.size() != 3) throw std::runtime_error("densify must hold (accum, denom, max_radius)");
+  for (const auto& t : d)
+    if (t.dim() != 1 || t.size(0) != in.P || t.scalar_type() != at::kFloat || t.device() != in.dev || !t.is_contiguous())
+      throw std::runtime_error("densify statistics must be contiguous fp32 (" + std::to_string(in.P) +
+                               ",) tensors on the device");
+  in.g.densify_accum = d[0].data_ptr<float>();
+  in.g.densify_denom = d[1].data_ptr<float>();
+  in.g.max_radius = d[2].data_ptr<float>();
+}
+
+// The backward's nine gradients in the order of its return tuple (_C.py
+// _buffer_shapes): fresh tensors, or the caller's `out` (empty, or nine
+// entries) -- with `exact` each in its exact shape (the GradientSink
+// contract), else an empty entry = allocate and the others matched by element
+// count and viewed in their shapes (a gradient bucket's flat views).
+std::vector<Tensor> gradient_outputs(const Inputs& in, const std::vector<Tensor>& out, bool exact) {
+  static const char* const names[9] = {"dmeans2D", "dcolors", "dsem", "dopacity", "dmeans3D",
+                                       "dcov3D", "dsh", "dscales", "drot"};
+  const int64_t P = in.P;
+  const std::vector<int64_t> shapes[9] = {{P, 3}, {P, 3}, {P, in.F}, {P, 1}, {P, 3}, {P, 6}, {P, in.M, 3}, {P, 3}, {P, 4}};
+  if (!out.empty() && out.size() != 9) throw std::runtime_error("out must hold the 9 gradient buffers");
+  std::vector<Tensor> o;
+  for (int i = 0; i < 9; ++i) {
+    if (out.empty() || (!exact && out[i].numel() == 0)) {
+      o.push_back(at::empty(shapes[i], at::TensorOptions().dtype(at::kFloat).device(in.dev)));
+      continue;
+    }
+    const Tensor& d = out[i];
+    const int64_t n = c10::multiply_integers(shapes[i]);
+    const bool fits = exact ? d.sizes() == at::IntArrayRef(shapes[i]) : d.numel() == n;
+    if (!fits || d.scalar_type() != at::kFloat || d.device() != in.dev || !d.is_contiguous())
+      throw std::runtime_error(std::string("gradient buffer ") + names[i] + " must be a contiguous fp32 device tensor of " +
+                               (exact ? "its exact shape" : std::to_string(n) + " elements"));
+    o.push_back(d.view(shapes[i]));
+  }
+  return o;
+}
+
+// `exact_out`, `accumulate`: _C._backward.  Returns the gradients summed over
+// the cameras, in gradient_outputs' order.
+std::vector<Tensor> backward_batch(
     const Tensor& bg, const Tensor& means3D, const Tensor& radii, const OptT& colors, const OptT& sem,
     const OptT& scales, const OptT& rotations, double scale_modifier, const OptT& cov3D, const Tensor& views,
     const Tensor& projs, const std::vector<double>& cx, const std::vector<double>& cy, const std::vector<double>& tx,
@@ -391,24 +315,22 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tenso
     const std::vector<int64_t>& num_instances, const OptT& binning, const Tensor& img, const Tensor& alphas,
     bool debug, int64_t compat, const OptT& grad_mask, c10::optional<std::vector<Tensor>> densify,
     const OptT& opacity, bool activate, const std::vector<std::vector<int64_t>>& windows,
-    const std::vector<Tensor>& out, const OptT& scratch_in, bool scratch_zeroed, int64_t stream) {
+    const std::vector<Tensor>& out, bool exact_out, bool accumulate, const OptT& scratch_in, bool scratch_zeroed,
+    int64_t stream) {
   if (activate && !present(opacity)) throw std::runtime_error("activate=True needs the raw opacities");
+  if (accumulate && out.empty()) throw std::runtime_error("accumulate needs the caller's gradient buffers");
   Inputs in(means3D, colors, sem, activate ? opacity : c10::nullopt, scales, rotations, scale_modifier, cov3D, sh,
             degree);
   if (activate) in.g.flags |= GS_FLAG_ACTIVATE;
-  const int64_t C = (int64_t)cx.size();
-  if (!out.empty() && out.size() != 9) throw std::runtime_error("out must hold the 9 gradient destinations");
+  if (accumulate) in.g.flags |= GS_FLAG_ACCUMULATE;
+  const int64_t C = (int64_t)cx.size(), P = in.P;
+  // rasterize_points.cu:160-161 takes H, W from dL_dout_color; an absent
+  // upstream gradient counts as zeros, sized from the alpha image
   const Tensor& img_ref = present(dL_color) ? *dL_color : alphas;
   const int64_t H = img_ref.size(-2), W = img_ref.size(-1);
   Cameras k(in.dev, bg, views, projs, campos, cx, cy, tx, ty, W, H, windows);
-  const auto f32 = at::TensorOptions().dtype(at::kFloat).device(in.dev);
-  const int64_t P = in.P;
   Tensor gm;
-  if (grad_mask.has_value() && grad_mask->defined()) {
-    gm = grad_mask->to(in.dev, at::kFloat).reshape({-1}).contiguous();
-    if (gm.numel() != P) throw std::runtime_error("grad_mask must have " + std::to_string(P) + " elements");
-    in.g.grad_mask = gm.data_ptr<float>();
-  }
+  set_grad_mask(in, grad_mask, gm);
   Tensor dLc = batch_image(dL_color, C, 3, H, W, in.dev, "dL_dout_color");
   Tensor dLd = batch_image(dL_depth, C, 1, H, W, in.dev, "dL_dout_depth");
   Tensor dLa = batch_image(dL_alpha, C, 1, H, W, in.dev, "dL_dout_alpha");
@@ -418,34 +340,8 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tenso
   if (radii_c.dim() != 2 || radii_c.size(0) != C || radii_c.size(1) != P)
     throw std::runtime_error("radii must be [C=" + std::to_string(C) + ", P=" + std::to_string(P) + "]");
   if ((int64_t)num_instances.size() != C) throw std::runtime_error("num_instances must have C entries");
-  const std::vector<std::vector<int64_t>> shapes = {{P, 3}, {P, 3}, {P, in.F}, {P, 1}, {P, 3},
-                                                    {P, 6}, {P, in.M, 3}, {P, 3}, {P, 4}};
-  // Caller-owned destinations (a gradient bucket's views): written, not
-  // accumulated; an empty tensor = allocate.
-  std::vector<Tensor> o;
-  for (int i = 0; i < 9; ++i) {
-    if (out.empty() || out[i].numel() == 0) {
-      o.push_back(at::empty(shapes[i], f32));
-      continue;
-    }
-    const Tensor& d = out[i];
-    int64_t n = 1;
-    for (int64_t e : shapes[i]) n *= e;
-    if (d.scalar_type() != at::kFloat || d.device() != in.dev || !d.is_contiguous() || d.numel() != n)
-      throw std::runtime_error("out[" + std::to_string(i) + "] must be a contiguous fp32 device tensor of " +
-                               std::to_string(n) + " elements");
-    o.push_back(d.view(shapes[i]));
-  }
-  if (densify.has_value()) {
-    const auto& d = *densify;
-    if (d.size() != 3) throw std::runtime_error("densify must hold (accum, denom, max_radius)");
-    for (const auto& t : d)
-      if (t.dim() != 1 || t.size(0) != P || t.scalar_type() != at::kFloat || t.device() != in.dev || !t.is_contiguous())
-        throw std::runtime_error("densify statistics must be contiguous fp32 (P,) tensors on the device");
-    in.g.densify_accum = d[0].data_ptr<float>();
-    in.g.densify_denom = d[1].data_ptr<float>();
-    in.g.max_radius = d[2].data_ptr<float>();
-  }
+  std::vector<Tensor> o = gradient_outputs(in, out, exact_out);
+  set_densify(in, densify);
   // the scratch: the caller's (kept from the forward, which may have zeroed
   // it: scratch_zeroed -> GS_FLAG_SCRATCH_ZEROED) or a fresh one
   const int64_t nscr = (int64_t)gs_batch_backward_scratch_bytes(P, (int32_t)in.F, (int32_t)C);
@@ -456,7 +352,7 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tenso
       throw std::runtime_error("scratch must be a contiguous device tensor of " + std::to_string(nscr) + " bytes");
     if (scratch_zeroed) in.g.flags |= GS_FLAG_SCRATCH_ZEROED;
   } else {
-    scratch = at::empty({nscr}, f32.dtype(at::kByte));
+    scratch = at::empty({nscr}, at::TensorOptions().dtype(at::kByte).device(in.dev));
   }
   const Tensor bin = binning.has_value() ? *binning : Tensor();
   auto fp = [](const Tensor& t) -> const float* { return t.defined() ? t.data_ptr<float>() : nullptr; };
@@ -467,8 +363,8 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tenso
                           o[4].data_ptr<float>(), o[5].data_ptr<float>(), static_cast<float*>(nz(o[6])),
                           o[7].data_ptr<float>(), o[8].data_ptr<float>(), reinterpret_cast<gs_stream_t>(stream)),
         "rasterize_gaussians_batch_backward");
-  Tensor dsem = in.F_user != in.F ? o[2].narrow(1, 0, in.F_user) : o[2];
-  return {o[0], o[1], dsem, o[3], o[4], o[5], o[6], o[7], o[8]};
+  if (in.F_user != in.F) o[2] = o[2].narrow(1, 0, in.F_user);
+  return o;
 }
 
 }  // namespace
@@ -476,8 +372,6 @@ std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tenso
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.doc() = "native fast path of dynamic3dgaussians_amd._C (C++ over the gsplat_hip C ABI)";
   m.def("abi_version", []() { return gs_version(); });
-  m.def("forward", &forward);
-  m.def("backward", &backward);
   m.def("forward_batch", &forward_batch);
   m.def("backward_batch", &backward_batch);
 }

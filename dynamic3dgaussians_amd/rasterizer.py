@@ -64,6 +64,60 @@ _FUSABLE_LABEL_DTYPES = (torch.float32, torch.float16, torch.bfloat16, torch.boo
                          torch.int8, torch.int16, torch.int32, torch.int64)
 
 
+def _fusable(label, means3D) -> bool:
+    """The label mask is fused into the backward kernel when that is
+    bit-identical to the wrapper's `grad * label.unsqueeze(1)` (a [P] label
+    whose dtype does not promote fp32); otherwise _input_grads applies it
+    exactly as the reference does."""
+    return (label is not None and label.dim() == 1 and label.numel() == means3D.size(0)
+            and label.dtype in _FUSABLE_LABEL_DTYPES)
+
+
+def _input_grads(grads, sem_shape, label, fuse):
+    """The binding's gradient tuple as the gradients of the autograd
+    functions' first nine inputs."""
+    (grad_means2D, grad_colors_precomp, grad_semantic_feature, grad_opacities, grad_means3D,
+     grad_cov3Ds_precomp, grad_sh, grad_scales, grad_rotations) = grads
+    if sem_shape is not None:
+        grad_semantic_feature = grad_semantic_feature.reshape(sem_shape)
+    else:
+        grad_semantic_feature = None
+    if label is not None and not fuse:
+        # __init__.py:159-173: every Gaussian-parameter gradient except
+        # means2D and the semantic feature is masked by `label` (Q12).
+        lab = label.unsqueeze(1)
+        grad_means3D = grad_means3D * lab
+        grad_sh = grad_sh * lab[..., None]
+        grad_colors_precomp = grad_colors_precomp * lab
+        grad_opacities = grad_opacities * lab
+        grad_scales = grad_scales * lab
+        grad_rotations = grad_rotations * lab
+        grad_cov3Ds_precomp = grad_cov3Ds_precomp * lab
+    return (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_semantic_feature,
+            grad_opacities, grad_scales, grad_rotations, grad_cov3Ds_precomp)
+
+
+def _check_inputs(shs, colors_precomp, scales, rotations, cov3D_precomp):
+    """__init__.py:214-218, texts unchanged."""
+    if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
+        raise Exception('Please provide excatly one of either SHs or precomputed colors!')
+    if ((scales is None or rotations is None) and cov3D_precomp is None) or \
+            ((scales is not None or rotations is not None) and cov3D_precomp is not None):
+        raise Exception('Please provide exactly one of either scale/rotation pair or '
+                        'precomputed 3D covariance!')
+
+
+def _by_generation(has_label, has_sem, color, radii, feature_map, depth, alpha):
+    """The caller generation's return tuple (module docstring)."""
+    if has_label and has_sem:      # G3 (vendored API)
+        return color, radii, feature_map, depth, alpha
+    if has_label:                  # G2
+        return color, radii, depth, alpha
+    if has_sem:                    # G4 (feature-3DGS style)
+        return color, feature_map, radii, depth
+    return color, radii, depth     # G1 (upstream "w-depth" API)
+
+
 class _RasterizeGaussians(torch.autograd.Function):
     """__init__.py:48-174."""
 
@@ -75,11 +129,8 @@ class _RasterizeGaussians(torch.autograd.Function):
         for name in ("bg", "viewmatrix", "projmatrix", "campos"):
             if getattr(raster_settings, name) is None:
                 raise TypeError(f"GaussianRasterizationSettings.{name} is required")
-        sh = _empty_like_none(sh)
-        colors_precomp = _empty_like_none(colors_precomp)
-        scales = _empty_like_none(scales)
-        rotations = _empty_like_none(rotations)
-        cov3Ds_precomp = _empty_like_none(cov3Ds_precomp)
+        sh, colors_precomp, scales, rotations, cov3Ds_precomp = map(
+            _empty_like_none, (sh, colors_precomp, scales, rotations, cov3Ds_precomp))
         # Argument order of the C++ binding (__init__.py:67-90)
         args = (raster_settings.bg, means3D, colors_precomp, semantic_feature, opacities, scales,
                 rotations, raster_settings.scale_modifier, cov3Ds_precomp,
@@ -131,12 +182,7 @@ class _RasterizeGaussians(torch.autograd.Function):
                 rs.scale_modifier, cov3Ds_precomp, rs.viewmatrix, rs.projmatrix, *cam4,
                 grad_color, grad_out_feature, grad_depth, grad_alpha, sh, rs.sh_degree, rs.campos,
                 geomBuffer, num_rendered, binningBuffer, imgBuffer, alpha, rs.debug)
-        # The label mask is fused into the backward kernel when that is
-        # bit-identical to the wrapper's `grad * label.unsqueeze(1)` (a [P]
-        # label whose dtype does not promote fp32); otherwise it is applied
-        # below exactly as the reference does.
-        fuse = (label is not None and label.dim() == 1 and label.numel() == means3D.size(0)
-                and label.dtype in _FUSABLE_LABEL_DTYPES)
+        fuse = _fusable(label, means3D)
         kw = dict(compat=ctx.compat, grad_mask=label if fuse else None)
         sink = getattr(rs, "grad_sink", None)
         if sink is not None and (label is None or fuse):
@@ -166,25 +212,7 @@ class _RasterizeGaussians(torch.autograd.Function):
                 raise ex
         else:
             grads = _C.rasterize_gaussians_backward(*args, **kw)
-        (grad_means2D, grad_colors_precomp, grad_semantic_feature, grad_opacities, grad_means3D,
-         grad_cov3Ds_precomp, grad_sh, grad_scales, grad_rotations) = grads
-        if ctx.sem_shape is not None:
-            grad_semantic_feature = grad_semantic_feature.reshape(ctx.sem_shape)
-        else:
-            grad_semantic_feature = None
-        if label is not None and not fuse:
-            # __init__.py:159-173: every Gaussian-parameter gradient except
-            # means2D and the semantic feature is masked by `label` (Q12).
-            lab = label.unsqueeze(1)
-            grad_means3D = grad_means3D * lab
-            grad_sh = grad_sh * lab[..., None]
-            grad_colors_precomp = grad_colors_precomp * lab
-            grad_opacities = grad_opacities * lab
-            grad_scales = grad_scales * lab
-            grad_rotations = grad_rotations * lab
-            grad_cov3Ds_precomp = grad_cov3Ds_precomp * lab
-        grads = (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_semantic_feature,
-                 grad_opacities, grad_scales, grad_rotations, grad_cov3Ds_precomp, None, None)
+        grads = _input_grads(grads, ctx.sem_shape, label, fuse) + (None, None)
         # inputs that were absent (None) or do not require grad get None
         return tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad))
 
@@ -356,31 +384,15 @@ class GaussianRasterizer(nn.Module):
         if getattr(rs, "tile_window", None) is not None:
             raise NotImplementedError("tile_window (image sharding) is a camera-batch feature: use "
                                       "GaussianRasterizerBatch")
-        if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
-            raise Exception('Please provide excatly one of either SHs or precomputed colors!')
-        if ((scales is None or rotations is None) and cov3D_precomp is None) or \
-                ((scales is not None or rotations is not None) and cov3D_precomp is not None):
-            raise Exception('Please provide exactly one of either scale/rotation pair or '
-                            'precomputed 3D covariance!')
+        _check_inputs(shs, colors_precomp, scales, rotations, cov3D_precomp)
         # __init__.py:218-230: absent inputs become empty tensors
-        shs = torch.Tensor([]) if shs is None else shs
-        colors_precomp = torch.Tensor([]) if colors_precomp is None else colors_precomp
-        scales = torch.Tensor([]) if scales is None else scales
-        rotations = torch.Tensor([]) if rotations is None else rotations
-        cov3D_precomp = torch.Tensor([]) if cov3D_precomp is None else cov3D_precomp
+        shs, colors_precomp, scales, rotations, cov3D_precomp = map(
+            _empty_like_none, (shs, colors_precomp, scales, rotations, cov3D_precomp))
         has_label = label is not _UNSET
         lab = label if (has_label and isinstance(label, torch.Tensor)) else None
-        color, radii, feature_map, depth, alpha = rasterize_gaussians(
-            means3D, means2D, shs, colors_precomp, semantic_feature, opacities, scales, rotations,
-            cov3D_precomp, rs, lab)
-        has_sem = semantic_feature is not None
-        if has_label and has_sem:      # G3 (vendored API)
-            return color, radii, feature_map, depth, alpha
-        if has_label:                  # G2
-            return color, radii, depth, alpha
-        if has_sem:                    # G4 (feature-3DGS style)
-            return color, feature_map, radii, depth
-        return color, radii, depth     # G1 (upstream "w-depth" API)
+        out = rasterize_gaussians(means3D, means2D, shs, colors_precomp, semantic_feature, opacities, scales,
+                                  rotations, cov3D_precomp, rs, lab)
+        return _by_generation(has_label, semantic_feature is not None, *out)
 
 
 # ---------------------------------------------------------------------------
@@ -442,11 +454,8 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
         compat = _compat_of(rs0)
         C = cams.C
         pp, views, projs, cpos = cams.pp, cams.views, cams.projs, cams.cpos
-        sh = _empty_like_none(sh)
-        colors_precomp = _empty_like_none(colors_precomp)
-        scales = _empty_like_none(scales)
-        rotations = _empty_like_none(rotations)
-        cov3Ds_precomp = _empty_like_none(cov3Ds_precomp)
+        sh, colors_precomp, scales, rotations, cov3Ds_precomp = map(
+            _empty_like_none, (sh, colors_precomp, scales, rotations, cov3Ds_precomp))
         tx, ty = cams.tx, cams.ty
         # the backward's scratch, zeroed by the forward's blend (whose HBM is
         # mostly idle) instead of a fill launch before the backward blend
@@ -472,8 +481,7 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
         ctx.densify_out = densify_out
         ctx.raw_params = raw_params
         ctx.grad_into = _grad_destinations(grad_into, semantic_feature)
-        if ctx.grad_into and isinstance(label, torch.Tensor) and not (
-                label.dim() == 1 and label.numel() == means3D.size(0) and label.dtype in _FUSABLE_LABEL_DTYPES):
+        if ctx.grad_into and isinstance(label, torch.Tensor) and not _fusable(label, means3D):
             raise ValueError("grad_into needs a per-Gaussian float label (applied in-kernel) or none")
         ctx.set_materialize_grads(False)
         ctx.sem_shape = None if semantic_feature is None else tuple(semantic_feature.shape)
@@ -493,8 +501,7 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
         cx, cy = [p[0] for p in pp], [p[1] for p in pp]
         # Q2 in reference mode, per camera (see _RasterizeGaussians.backward)
         cam4 = (tx, ty, cx, cy) if ctx.compat == "reference" else (cx, cy, tx, ty)
-        fuse = (label is not None and label.dim() == 1 and label.numel() == means3D.size(0)
-                and label.dtype in _FUSABLE_LABEL_DTYPES)
+        fuse = _fusable(label, means3D)
         grads = _C.rasterize_gaussians_batch_backward(
             rs0.bg, means3D, radii, colors_precomp, semantic_feature, scales, rotations, rs0.scale_modifier,
             cov3Ds_precomp, views, projs, *cam4, grad_color, grad_out_feature, grad_depth, grad_alpha, sh,
@@ -503,27 +510,10 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
             activate=ctx.raw_params, windows=windows, out=ctx.grad_into, scratch=ctx.scratch,
             scratch_zeroed=ctx.scratch_zeroed)
         ctx.scratch_zeroed = False  # a second backward (retain_graph) finds it written
-        (grad_means2D, grad_colors_precomp, grad_semantic_feature, grad_opacities, grad_means3D,
-         grad_cov3Ds_precomp, grad_sh, grad_scales, grad_rotations) = grads
-        if ctx.sem_shape is not None:
-            grad_semantic_feature = grad_semantic_feature.reshape(ctx.sem_shape)
-        else:
-            grad_semantic_feature = None
-        if label is not None and not fuse:
-            if ctx.raw_params:
-                raise RuntimeError("raw_params=True needs a per-Gaussian fp32 label (or none): the mask is "
-                                   "applied in-kernel before the activations' backward")
-            lab = label.unsqueeze(1)
-            grad_means3D = grad_means3D * lab
-            grad_sh = grad_sh * lab[..., None]
-            grad_colors_precomp = grad_colors_precomp * lab
-            grad_opacities = grad_opacities * lab
-            grad_scales = grad_scales * lab
-            grad_rotations = grad_rotations * lab
-            grad_cov3Ds_precomp = grad_cov3Ds_precomp * lab
-        grads = (grad_means3D, grad_means2D, grad_sh, grad_colors_precomp, grad_semantic_feature,
-                 grad_opacities, grad_scales, grad_rotations, grad_cov3Ds_precomp, None, None, None, None, None,
-                 None, None, None)
+        if label is not None and not fuse and ctx.raw_params:
+            raise RuntimeError("raw_params=True needs a per-Gaussian fp32 label (or none): the mask is "
+                               "applied in-kernel before the activations' backward")
+        grads = _input_grads(grads, ctx.sem_shape, label, fuse) + (None,) * 8
         # gradients written into caller-owned destinations: autograd gets None
         taken = [False] * len(grads)
         for k in (ctx.grad_into or {}):
@@ -675,17 +665,9 @@ class GaussianRasterizerBatch(nn.Module):
         semantic_feature (gs_gaussians.feature_ready).  `grad_into` (keyword,
         optional): {argument name: tensor} destinations the backward writes
         those gradients into (rasterize_gaussians_batch)."""
-        if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
-            raise Exception('Please provide excatly one of either SHs or precomputed colors!')
-        if ((scales is None or rotations is None) and cov3D_precomp is None) or \
-                ((scales is not None or rotations is not None) and cov3D_precomp is not None):
-            raise Exception('Please provide exactly one of either scale/rotation pair or '
-                            'precomputed 3D covariance!')
-        shs = torch.Tensor([]) if shs is None else shs
-        colors_precomp = torch.Tensor([]) if colors_precomp is None else colors_precomp
-        scales = torch.Tensor([]) if scales is None else scales
-        rotations = torch.Tensor([]) if rotations is None else rotations
-        cov3D_precomp = torch.Tensor([]) if cov3D_precomp is None else cov3D_precomp
+        _check_inputs(shs, colors_precomp, scales, rotations, cov3D_precomp)
+        shs, colors_precomp, scales, rotations, cov3D_precomp = map(
+            _empty_like_none, (shs, colors_precomp, scales, rotations, cov3D_precomp))
         has_label = label is not _UNSET
         lab = label if (has_label and isinstance(label, torch.Tensor)) else None
         dens = None
@@ -693,15 +675,8 @@ class GaussianRasterizerBatch(nn.Module):
             P = means3D.size(0)
             dens = tuple(torch.zeros(P, dtype=torch.float32, device=means3D.device) for _ in range(3))
             self.densify_stats = {"means2D_gradient_accum": dens[0], "denom": dens[1], "max_2D_radius": dens[2]}
-        color, radii, feature_map, depth, alpha = rasterize_gaussians_batch(
+        out = rasterize_gaussians_batch(
             means3D, means2D, shs, colors_precomp, semantic_feature, opacities, scales, rotations,
             cov3D_precomp, self._cams, lab, dens, self.raw_params, feature_ready, self.plan, grad_into,
             self._walk_order(means3D))
-        has_sem = semantic_feature is not None
-        if has_label and has_sem:      # G3
-            return color, radii, feature_map, depth, alpha
-        if has_label:                  # G2
-            return color, radii, depth, alpha
-        if has_sem:                    # G4
-            return color, feature_map, radii, depth
-        return color, radii, depth     # G1
+        return _by_generation(has_label, semantic_feature is not None, *out)

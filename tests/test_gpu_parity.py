@@ -416,6 +416,111 @@ def test_native_binding_matches_ctypes_binding(F, Fp):
     assert H.rel_l2(xa["dmeans3D"], 2 * ba[4]) <= 1e-5
 
 
+def _backward_args(inp, fwd, grads):
+    num_rendered, color, feat, depth, alpha, radii, geom, binning, img = fwd
+    d = lambda k: H._to(inp[k], H.DEV)  # noqa: E731
+    return (d("bg"), d("means3D"), radii, d("colors"), d("semantic_feature"), d("scales"), d("rotations"),
+            inp["scale_modifier"], d("cov3D_precomp"), d("viewmatrix"), d("projmatrix"), *H.bwd_cam4(inp, True),
+            *[t.to(H.DEV) for t in grads], d("sh"), inp["degree"], d("campos"), geom, num_rendered, binning, img,
+            alpha, False)
+
+
+def test_single_camera_abi_entry_points_match_the_binding():
+    """gs_forward_plan / gs_forward_render / gs_backward -- the reference-shaped
+    single-camera entry points of the C ABI, which the
+    package itself reaches only as a batch of one -- driven with ctypes
+    directly: outputs bit-equal to _C.rasterize_gaussians, gradients equal to
+    _C.rasterize_gaussians_backward up to the atomic backward's summation
+    order."""
+    import ctypes
+    P, F, W, Hh = 3000, 8, 96, 80
+    inp = H.scene(P=P, F=F, W=W, H=Hh)
+    grads = H.upstream_grads(Hh, W, F)
+    ref_f = H.gpu_forward(inp)
+    ref_b = H.gpu_backward(inp, ref_f, grads)
+
+    L_ = _lib.load()
+    t = {k: H._to(inp[k], H.DEV).float().contiguous() for k in (
+        "bg", "means3D", "colors", "semantic_feature", "opacity", "scales", "rotations", "viewmatrix",
+        "projmatrix", "campos")}
+    assert t["semantic_feature"].numel() == P * F
+    p = lambda x: x.data_ptr() if x.numel() else None  # noqa: E731
+    g = _lib.GsGaussians(P=P, D=0, M=0, F=F, means3D=p(t["means3D"]), colors_precomp=p(t["colors"]),
+                         semantic_feature=p(t["semantic_feature"]), opacities=p(t["opacity"]),
+                         scales=p(t["scales"]), rotations=p(t["rotations"]), scale_modifier=1.0)
+
+    def camera(c_x, c_y, tan_fovx, tan_fovy):
+        return _lib.GsCamera(viewmatrix=p(t["viewmatrix"]), projmatrix=p(t["projmatrix"]), campos=p(t["campos"]),
+                             background=p(t["bg"]), c_x=c_x, c_y=c_y, tan_fovx=tan_fovx, tan_fovy=tan_fovy,
+                             image_width=W, image_height=Hh)
+    dev = t["means3D"].device
+    f32 = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)  # noqa: E731
+    u8 = lambda n: torch.empty(max(1, n), dtype=torch.uint8, device=dev)  # noqa: E731
+    color, feat, depth, alpha = f32(3, Hh, W), f32(F, Hh, W), f32(1, Hh, W), f32(1, Hh, W)
+    radii = torch.empty(P, dtype=torch.int32, device=dev)
+    geom, img = u8(L_.gs_geom_buffer_bytes(P)), u8(L_.gs_image_buffer_bytes(W, Hh))
+    s = _lib.stream(dev)
+    cam = camera(inp["c_x"], inp["c_y"], inp["tan_fovx"], inp["tan_fovy"])
+    NR, NI = ctypes.c_int64(0), ctypes.c_int64(0)
+    _lib.check(L_.gs_forward_plan(ctypes.byref(g), ctypes.byref(cam), 0, 0, 0, p(geom), p(img), p(radii),
+                                  ctypes.byref(NR), ctypes.byref(NI), s), "gs_forward_plan")
+    assert 0 < NI.value <= NR.value
+    binning = u8(L_.gs_binning_buffer_bytes(NI.value))
+    _lib.check(L_.gs_forward_render(ctypes.byref(g), ctypes.byref(cam), 0, 0, p(geom), p(binning), p(img), NI.value,
+                                    p(radii), p(color), p(feat), p(depth), p(alpha), s), "gs_forward_render")
+    torch.cuda.synchronize()
+    assert NR.value == ref_f[0]
+    for name, a, b in zip(("color", "feature_map", "depth", "alpha", "radii"), (color, feat, depth, alpha, radii),
+                          ref_f[1:6]):
+        assert a.shape == b.shape and torch.equal(a, b), name
+
+    # the backward as the binding runs it in reference mode (Q2: swapped camera scalars)
+    bcam = camera(*H.bwd_cam4(inp, True))
+    dc, df, dd, da = [x.to(dev).contiguous() for x in grads]
+    out = _C.backward_buffers(P, F, 0, dev)
+    scratch = u8(L_.gs_backward_scratch_bytes(P, F))
+    _lib.check(L_.gs_backward(ctypes.byref(g), ctypes.byref(bcam), p(radii), 0, 0, p(geom), p(binning), p(img),
+                              NR.value, p(alpha), p(dc), p(df), p(dd), p(da), p(scratch),
+                              *[p(out[k]) for k in _C._BUFFER_ORDER], s), "gs_backward")
+    torch.cuda.synchronize()
+    for k, b in zip(_C._BUFFER_ORDER, ref_b):
+        a = out[k].cpu().numpy()
+        assert a.shape == b.shape, k
+        assert H.rel_l2(a, b) <= 1e-5 or (not a.any() and not b.any()), k
+
+
+@pytest.mark.parametrize("mode", ["native", "ctypes"])
+def test_backward_out_contract_is_checked_before_any_launch(mode):
+    """rasterize_gaussians_backward(out=...) takes the GradientSink contract
+    only: every gradient name, each in its exact shape (a buffer of the right
+    element count but another shape is refused), and accumulate=True needs
+    `out`.  Each bad call raises before any launch: the buffers are untouched."""
+    from dynamic3dgaussians_amd import _C as C
+    P, F = 3000, 8
+    inp = H.scene(P=P, F=F, W=96, H=80)
+    args = _backward_args(inp, H.gpu_forward(inp), H.upstream_grads(80, 96, F))
+    bufs = C.backward_buffers(P, F, 0, H.DEV)
+    for v in bufs.values():
+        v.fill_(7.0)
+    assert C.native_loaded()
+    keep = C._native
+    try:
+        C._native = keep if mode == "native" else None
+        reshaped = dict(bufs, dmeans3D=torch.full((3, P), 7.0, device=H.DEV))
+        with pytest.raises(RuntimeError, match="dmeans3D"):
+            C.rasterize_gaussians_backward(*args, out=reshaped)
+        missing = {k: v for k, v in bufs.items() if k != "dcov3D"}
+        with pytest.raises(RuntimeError, match="dcov3D"):
+            C.rasterize_gaussians_backward(*args, out=missing)
+        with pytest.raises(ValueError, match="accumulate=True needs"):
+            C.rasterize_gaussians_backward(*args, out=None, accumulate=True)
+    finally:
+        C._native = keep
+    torch.cuda.synchronize()
+    for k, v in {**bufs, "reshaped": reshaped["dmeans3D"]}.items():
+        assert torch.equal(v, torch.full_like(v, 7.0)), k
+
+
 def test_debug_mode_validates_and_passes_on_a_valid_scene():
     """debug=True: the forward checks its plan header, ranges and list ids on
     the host (gs_check_*, gsplat_hip.h) before the blend; a valid scene
