@@ -12,6 +12,8 @@ Layout:
   distributed.py  camera-sharded data parallelism with one RCCL all-reduce
   image_loss.py   the reference's L1 + SSIM photometric loss, fused (include/gs_loss.h)
   depth_loss.py   the reference's masked depth-correlation (Pearson) loss, fused (include/gs_depth_loss.h)
+  resample.py     the reference's bilinear F.interpolate to a prior's size, deterministic (include/gs_resample.h)
+  feature_loss.py the reference's feature-distillation loss: resample to the prior, then L1 (+ SSIM)
   densify.py      the reference's clone / split / prune with the Adam state (include/gs_densify.h)
   motion.py       the reference's motion-basis warp: SE(3) basis blend, fused (include/gs_motion.h)
 """
@@ -20,6 +22,8 @@ from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, Grad
 from ._C import set_default_compat, get_default_compat  # noqa: F401
 from .image_loss import photometric_image_loss, photometric_loss, photometric_loss_torch  # noqa: F401
 from .depth_loss import depth_correlation_loss, depth_correlation_loss_torch  # noqa: F401
+from .resample import bilinear_resize, bilinear_resize_torch  # noqa: F401
+from .feature_loss import distillation_image_loss, feature_distillation_loss  # noqa: F401
 # `densify` here is the function; its module (schedule, plan, classify_torch, ...) is
 # importlib.import_module('dynamic3dgaussians_amd.densify')
 from .densify import densify, densify_torch  # noqa: F401

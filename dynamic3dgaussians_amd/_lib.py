@@ -70,6 +70,13 @@ class GsDepthLoss(ctypes.Structure):
                 ("workspace_bytes", ctypes.c_uint64)]
 
 
+class GsResample(ctypes.Structure):
+    """include/gs_resample.h gs_resample."""
+    _fields_ = [("B", c_int32), ("Ch", c_int32), ("H", c_int32), ("W", c_int32), ("h", c_int32), ("w", c_int32),
+                ("align_corners", c_int32), ("x", c_void_p), ("y", c_void_p), ("workspace", c_void_p),
+                ("workspace_bytes", ctypes.c_uint64)]
+
+
 GS_DENSIFY_MAX_TENSORS = 16  # include/gs_densify.h
 GS_DENSIFY_N_SPLIT = 2
 GS_DENSIFY_ROLES = {"plain": 0, "means": 1, "log_scales": 2, "rotations": 3, "logit_opacities": 4}
@@ -217,6 +224,13 @@ PROTOTYPES = {
     "gs_depth_loss_validate": (ctypes.c_int, [ctypes.POINTER(GsDepthLoss), ctypes.c_int, c_void_p, c_void_p]),
     "gs_depth_loss_forward": (ctypes.c_int, [ctypes.POINTER(GsDepthLoss), c_void_p]),
     "gs_depth_loss_backward": (ctypes.c_int, [ctypes.POINTER(GsDepthLoss), c_void_p, c_void_p, c_void_p]),
+    # include/gs_resample.h
+    "gs_resample_struct_bytes": (c_size_t, []),
+    "gs_resample_workspace_bytes": (c_size_t, [c_int32, c_int32]),
+    "gs_resample_validate": (ctypes.c_int, [ctypes.POINTER(GsResample), ctypes.c_int, c_void_p, c_void_p]),
+    "gs_resample_axis": (ctypes.c_int, [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    "gs_resample_forward": (ctypes.c_int, [ctypes.POINTER(GsResample), c_void_p]),
+    "gs_resample_backward": (ctypes.c_int, [ctypes.POINTER(GsResample), c_void_p, c_void_p, c_void_p]),
     # include/gs_densify.h
     "gs_densify_plan_struct_bytes": (c_size_t, []),
     "gs_densify_tensor_struct_bytes": (c_size_t, []),

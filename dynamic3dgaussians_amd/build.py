@@ -48,6 +48,8 @@ VARIANT_FLAGS = {"": [], "stats": ["-DGS_STATS"], "stamps": ["-DGS_STAMPS"],
                  # the motion warp's two measured alternatives: a lane per (g, b) in the
                  # forward, store-and-sum for the basis gradients
                  "motion_alt": ["-DGS_MOTION_FWD_PAIR", "-DGS_MOTION_STORE_SUM"],
+                 # the resample backward's measured alternative: one plane per step, not four
+                 "rs_pb1": ["-DGS_RS_PLANE_BATCH=1"],
                  "ctl": []}  # the product's flags under a variant's (ctypes) binding: the A/B control
 PATCHED = ("exp_nofeat", "exp_noacc", "exp_noatomic", "exp_fwd_nofeatst", "exp_sort_copy", "exp_rot_all", "exp_fwd_row0")
 ARCH = os.environ.get("GSPLAT_OFFLOAD_ARCH", "gfx950")
@@ -66,12 +68,14 @@ SOURCES = {
     "gs_densify.hip": ["-ffp-contract=off"],
     "gs_motion.hip": [],
     "gs_depth_loss.hip": [],
+    "gs_resample.hip": [],
     "gs_api.hip": [],
     "gs_host.cpp": [],  # host-only C++ (also built by oracle/Makefile's sanitizer target)
     "gs_densify_host.cpp": [],  # host-only C++ (also built into tools/densify_host_sanitize.c's program)
     "gs_loss_host.cpp": [],  # host-only C++ (also built into tools/loss_host_sanitize.c's program)
     "gs_motion_host.cpp": [],  # host-only C++ (also built into tools/motion_host_sanitize.c's program)
     "gs_depth_loss_host.cpp": [],  # host-only C++ (also built into tools/depth_loss_host_sanitize.c's program)
+    "gs_resample_host.cpp": [],  # host-only C++ (also built into tools/resample_host_sanitize.c's program)
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall",
           "-Wno-unused-function", "-I", CSRC, "-I", INCLUDE]
