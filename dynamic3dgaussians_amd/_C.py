@@ -3,10 +3,14 @@
 Reference: DGR/ext.cpp:15-19 and DGR/rasterize_points.cu:35-246 (DGR =
 submodules_fsgs/diff-gaussian-rasterization-confidence).  The three functions
 keep the reference's exact positional signatures and return tuples, so the
-reference's own autograd wrapper could call them unchanged; they allocate
-outputs with torch (caching allocator) and hand raw device pointers to the
-HIP C ABI (libgsplat_hip.so).  There is no CPU fallback: non-device inputs or
-a missing library raise.
+reference's own autograd wrapper could call them unchanged.  Their arguments
+are marshalled by the C++ binding (csrc/gs_torch_binding.cpp, a torch
+extension next to the library): it allocates outputs with torch (caching
+allocator) and hands raw device pointers to the HIP C ABI (libgsplat_hip.so).
+This module keeps what is cheaper or clearer in Python in front of it: the
+answers for an empty scene, the `out`-name checks and the sync-free plan's
+bookkeeping.  There is no CPU fallback and no second binding: non-device
+inputs, a missing library or a missing extension raise.
 
 Superset behaviour (documented in DESIGN.md "Boundary"):
   * semantic_feature may be None/empty (F = 0), [P, F] or [P, 1, F]; any F is
@@ -16,59 +20,47 @@ Superset behaviour (documented in DESIGN.md "Boundary"):
 """
 from __future__ import annotations
 
-import ctypes
 import importlib.util
 import math
 import os
-import warnings
 
 import torch
 
 from . import _lib
-from ._lib import GsCamera, GsGaussians, check
+from ._lib import check
 
 _default_compat = "reference"
 
-# Native fast path (csrc/gs_torch_binding.cpp, lib/_gs_native.so): the same
-# argument handling in C++ over the same C ABI (forward_batch / backward_batch,
-# the counterparts of rasterize_gaussians_batch / _backward below), ~0.2 ms
-# less host time per camera than the ctypes code, which stays the documented
-# binding (and serves P == 0, CPU-tensor errors, build variants and
-# GS_NATIVE_BINDING=0).
-_native = None
-_native_tried = False
+_native = None  # the C++ binding (csrc/gs_torch_binding.cpp), once loaded
 
 
 def _native_mod():
-    global _native, _native_tried
-    if _native_tried:
+    """The C++ binding, loaded by the library's own rule (_lib.load): rebuilt
+    first when it is older than its source, a public header or the library."""
+    global _native
+    if _native is not None:
         return _native
-    _native_tried = True
-    if os.environ.get("GS_NATIVE_BINDING", "1") == "0" or _lib._build.VARIANT:
-        return None  # variants: the extension is linked against the product library
-    path = os.path.join(os.path.dirname(_lib.lib_path()), "_gs_native.so")
-    if not os.path.exists(path):
-        return None
     _lib.load()
-    if _lib._build.native_is_stale():
-        # older than its source, a public header or libgsplat_hip.so: its
-        # argument handling may not match the library -- serve the calls
-        # through the ctypes binding instead (same kernels, more host time)
-        warnings.warn("lib/_gs_native.so is stale (rebuild with `python -m dynamic3dgaussians_amd.build`); "
-                      "using the ctypes binding", RuntimeWarning)
-        return None
-    spec = importlib.util.spec_from_file_location("_gs_native", path)
+    build = _lib._build
+    path = build.NATIVE
+    try:
+        if build.native_is_stale():
+            build.build_native()
+    except Exception as ex:  # no toolchain, or a compile error
+        raise _lib.GsplatError(f"{os.path.basename(path)} is missing or older than its sources and could not be "
+                               f"rebuilt ({ex}); build it with `python -m dynamic3dgaussians_amd.build`") from None
+    spec = importlib.util.spec_from_file_location(build.NATIVE_NAME, path)
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
     if mod.abi_version() != _lib.ABI_VERSION:
-        raise _lib.GsplatError(f"_gs_native.so was built for ABI {mod.abi_version()}, the library is "
+        raise _lib.GsplatError(f"{os.path.basename(path)} was built for ABI {mod.abi_version()}, the library is "
                                f"{_lib.ABI_VERSION}; rebuild with `python -m dynamic3dgaussians_amd.build`")
     _native = mod
     return _native
 
 
 def native_loaded() -> bool:
-    """Whether the C++ fast path serves the calls (tests / diagnostics)."""
+    """Whether the C++ binding is loaded (loads it; tests / diagnostics)."""
     return _native_mod() is not None
 
 
@@ -100,10 +92,6 @@ def _dev(t: torch.Tensor, device, name: str) -> torch.Tensor:
     return t.contiguous()
 
 
-def _ptr(t) -> int | None:
-    return t.data_ptr() if t is not None else None
-
-
 def _feature_width(F: int) -> int:
     for k in _lib.SUPPORTED_F:
         if k >= F:
@@ -119,57 +107,14 @@ def _compat_code(compat) -> int:
     return _lib.GS_COMPAT[mode]
 
 
-class _Inputs:
-    """Device-resident, contiguous views of the per-Gaussian inputs."""
-
-    def __init__(self, means3D, colors, semantic_feature, opacity, scales, rotations,
-                 scale_modifier, cov3D_precomp, sh, degree):
-        if means3D.ndimension() != 2 or means3D.size(1) != 3:
-            raise RuntimeError("means3D must have dimensions (num_points, 3)")  # rasterize_points.cu:60-62
-        dev = means3D.device
-        if dev.type != "cuda":
-            raise _lib.GsplatError("the HIP rasterizer needs device tensors (means3D is on the CPU)")
-        self.device = dev
-        self.P = P = means3D.size(0)
-        self.means3D = _dev(means3D, dev, "means3D")
-        self.colors = _dev(colors, dev, "colors_precomp") if _present(colors) else None
-        self.opacity = _dev(opacity, dev, "opacities") if _present(opacity) else None
-        self.scales = _dev(scales, dev, "scales") if _present(scales) else None
-        self.rotations = _dev(rotations, dev, "rotations") if _present(rotations) else None
-        self.cov3D = _dev(cov3D_precomp, dev, "cov3D_precomp") if _present(cov3D_precomp) else None
-        self.sh = _dev(sh, dev, "sh") if _present(sh) else None
-        self.M = self.sh.size(1) if self.sh is not None else 0
-        self.D = int(degree)
-        self.scale_modifier = float(scale_modifier)
-        if _present(semantic_feature):
-            sem = _dev(semantic_feature, dev, "semantic_feature").reshape(P, -1)
-            self.F_user = sem.size(1)
-            self.F = _feature_width(self.F_user)
-            if self.F != self.F_user:
-                sem = torch.nn.functional.pad(sem, (0, self.F - self.F_user))
-            self.sem = sem.contiguous()
-        else:
-            self.F_user, self.F, self.sem = 0, 0, None
-
-    def struct(self, flags: int = 0) -> GsGaussians:
-        return GsGaussians(P=self.P, D=self.D, M=self.M, F=self.F,
-                           means3D=_ptr(self.means3D), shs=_ptr(self.sh),
-                           colors_precomp=_ptr(self.colors), semantic_feature=_ptr(self.sem),
-                           opacities=_ptr(self.opacity), scales=_ptr(self.scales),
-                           rotations=_ptr(self.rotations), cov3D_precomp=_ptr(self.cov3D),
-                           scale_modifier=self.scale_modifier, flags=flags, grad_mask=None,
-                           densify_accum=None, densify_denom=None, max_radius=None)
-
-
-def _native_serves(nat, means3D) -> bool:
-    """The C++ fast path takes the call; P == 0 and the argument errors of
-    host tensors are answered by the ctypes code."""
-    return nat is not None and means3D.is_cuda and means3D.dim() == 2 and means3D.size(0) > 0
-
-
-def _user_width(t, dim, inp):
-    """An output of the compiled feature width cut back to the caller's."""
-    return t.narrow(dim, 0, inp.F_user) if inp.F_user != inp.F else t
+def _num_points(means3D) -> int:
+    """P of a call, after the two checks every call answers before anything
+    else is looked at."""
+    if means3D.ndimension() != 2 or means3D.size(1) != 3:
+        raise RuntimeError("means3D must have dimensions (num_points, 3)")  # rasterize_points.cu:60-62
+    if means3D.device.type != "cuda":
+        raise _lib.GsplatError("the HIP rasterizer needs device tensors (means3D is on the CPU)")
+    return means3D.size(0)
 
 
 # A single camera is a batch of one: the two functions below wrap their
@@ -321,30 +266,6 @@ def mark_visible(means3D, viewmatrix, projmatrix):
 # of every call, the single-camera functions above included (C = 1, where the
 # batch entry points run exactly what the single-camera ones run).
 
-def _camera_batch(dev, background, viewmatrices, projmatrices, campos, c_x, c_y, tan_fovx, tan_fovy, W, H,
-                  windows=None):
-    C = len(c_x)
-    if windows is not None and len(windows) != C:
-        raise RuntimeError("tile windows: one (x0, y0, x1, y1) per camera")
-    if not (1 <= C <= 64):
-        raise _lib.GsplatError(f"camera batch size {C} outside 1..64")
-    if not (len(c_y) == len(tan_fovx) == len(tan_fovy) == C):
-        raise RuntimeError("per-camera scalars must all have C entries")
-    view = _dev(viewmatrices, dev, "viewmatrices").reshape(C, 16).contiguous()
-    proj = _dev(projmatrices, dev, "projmatrices").reshape(C, 16).contiguous()
-    cpos = _dev(campos, dev, "campos").reshape(C, 3).contiguous()
-    bg = _dev(background, dev, "bg").reshape(-1)
-    cams = (GsCamera * C)()
-    for c in range(C):
-        cams[c] = GsCamera(viewmatrix=view.data_ptr() + 64 * c, projmatrix=proj.data_ptr() + 64 * c,
-                           campos=cpos.data_ptr() + 12 * c, background=bg.data_ptr(), c_x=float(c_x[c]),
-                           c_y=float(c_y[c]), tan_fovx=float(tan_fovx[c]), tan_fovy=float(tan_fovy[c]),
-                           image_width=int(W), image_height=int(H))
-        if windows is not None and windows[c] is not None:
-            cams[c].tile_x0, cams[c].tile_y0, cams[c].tile_x1, cams[c].tile_y1 = (int(v) for v in windows[c])
-    return cams, [view, proj, cpos, bg]
-
-
 def _event_handle(ev) -> int:
     """The hipEvent_t of a recorded torch.cuda.Event (0 = none)."""
     return 0 if ev is None else int(ev.cuda_event)
@@ -436,107 +357,41 @@ def rasterize_gaussians_batch(background, means3D, colors, semantic_feature, opa
     device tensor the blend zeroes (its whole bytes, rounded down to 16) --
     the backward's scratch, handed to rasterize_gaussians_batch_backward
     with scratch_zeroed=True (gs_gaussians.zero_fill, ABI 13)."""
-    L_ = _lib.load()
     sync_free = plan_state is not None and not debug
     cm = _compat_code(compat)
+    P, C = _num_points(means3D), len(c_x)
+    if P == 0:  # answered before any camera argument is looked at
+        H, W = int(image_height), int(image_width)
+        f32 = dict(dtype=torch.float32, device=means3D.device)
+        u8 = dict(dtype=torch.uint8, device=means3D.device)
+        return ([0] * C, torch.zeros(C, 3, H, W, **f32), torch.zeros(C, 0, H, W, **f32),
+                torch.zeros(C, 1, H, W, **f32), torch.zeros(C, 1, H, W, **f32),
+                torch.zeros(C, 0, dtype=torch.int32, device=means3D.device), torch.empty(0, **u8),
+                torch.empty(0, **u8), torch.empty(0, **u8), [0] * C)
     if feature_ready is not None and _present(semantic_feature):
         sf = semantic_feature
-        Fu = sf.numel() // max(means3D.size(0), 1)
+        Fu = sf.numel() // P
         if not (sf.is_cuda and sf.dtype == torch.float32 and sf.is_contiguous() and _feature_width(Fu) == Fu):
             # the binding copies / pads the features on the calling stream
             # before any kernel runs: that copy has to wait too
             torch.cuda.current_stream(means3D.device).wait_event(feature_ready)
             feature_ready = None
-    nat = _native_mod()
-    C = len(c_x)
-    if _native_serves(nat, means3D):
-        cap = plan_state.next_capacity(C) if sync_free else []
-        try:
-            out = nat.forward_batch(background, means3D, _opt(colors), _opt(semantic_feature), _opt(opacity),
-                                    _opt(scales), _opt(rotations), float(scale_modifier), _opt(cov3D_precomp),
-                                    viewmatrices, projmatrices, [float(x) for x in c_x], [float(x) for x in c_y],
-                                    [float(x) for x in tan_fovx], [float(x) for x in tan_fovy], int(image_height),
-                                    int(image_width), _opt(sh), int(degree), campos, bool(prefiltered),
-                                    bool(debug), cm, bool(activate), _windows_arg(windows),
-                                    _event_handle(feature_ready), cap,
-                                    plan_state.hint if sync_free else [], _opt(walk_order), _opt(zero_fill),
-                                    _lib.stream(means3D.device))
-        except RuntimeError as ex:
-            raise _lib.GsplatError(str(ex)) from None
-        NR, color, fmap, depth, alpha, radii, geom, binning, img, NI, layout, hint, fitted = out
-        if sync_free:
-            plan_state.update(NI, hint, fitted, first=not any(cap))
-            return (NR, color, fmap, depth, alpha, radii, geom, binning, img, layout)
-        return (NR, color, fmap, depth, alpha, radii, geom, binning, img, NI)
-    inp = _Inputs(means3D, colors, semantic_feature, opacity, scales, rotations, scale_modifier,
-                  cov3D_precomp, sh, degree)
-    dev, P = inp.device, inp.P
-    H, W = int(image_height), int(image_width)
-    f32 = dict(dtype=torch.float32, device=dev)
-    u8 = dict(dtype=torch.uint8, device=dev)
-    if P == 0:  # answered before any camera argument is looked at
-        return ([0] * C, torch.zeros(C, 3, H, W, **f32), torch.zeros(C, inp.F_user, H, W, **f32),
-                torch.zeros(C, 1, H, W, **f32), torch.zeros(C, 1, H, W, **f32),
-                torch.zeros(C, 0, dtype=torch.int32, device=dev), torch.empty(0, **u8), torch.empty(0, **u8),
-                torch.empty(0, **u8), [0] * C)
-    cams, keep = _camera_batch(dev, background, viewmatrices, projmatrices, campos, c_x, c_y, tan_fovx,
-                               tan_fovy, W, H, windows)
-    g = inp.struct(_lib.GS_FLAG_ACTIVATE if activate else 0)
-    g.feature_ready = _event_handle(feature_ready) or None
-    if walk_order is not None:
-        if not (walk_order.is_cuda and walk_order.dtype == torch.int32 and walk_order.is_contiguous()
-                and walk_order.numel() == inp.P and walk_order.device == dev):
-            raise RuntimeError("walk_order must be a contiguous int32 device tensor of P ids")
-        g.walk_order = walk_order.data_ptr()
-    if zero_fill is not None:
-        if not (zero_fill.is_contiguous() and zero_fill.device == dev):
-            raise RuntimeError("zero_fill must be a contiguous device tensor")
-        g.zero_fill = zero_fill.data_ptr()
-        g.zero_fill_bytes = (zero_fill.numel() * zero_fill.element_size()) & ~15
-    out_color = torch.empty(C, 3, H, W, **f32)
-    out_feature = torch.empty(C, inp.F, H, W, **f32)
-    out_depth = torch.empty(C, 1, H, W, **f32)
-    # Q1: the reference never writes out_alpha (it stays 0; the kernel stores
-    # those zeros); "fixed" writes 1 - T.
-    out_alpha = torch.empty(C, 1, H, W, **f32)
-    radii = torch.empty(C, P, dtype=torch.int32, device=dev)
-    geom = torch.empty(L_.gs_batch_geom_buffer_bytes(P, C), **u8)
-    img = torch.empty(L_.gs_batch_image_buffer_bytes(W, H, C), **u8)
-    stream = _lib.stream(dev)
-    NR = (ctypes.c_int64 * C)()
-    NI = (ctypes.c_int64 * C)()
-    outs = (out_color.data_ptr(), out_feature.data_ptr() if inp.F else None, out_depth.data_ptr(),
-            out_alpha.data_ptr())
-    fitted = False
+    cap = plan_state.next_capacity(C) if sync_free else []
+    try:
+        out = _native_mod().forward_batch(
+            background, means3D, _opt(colors), _opt(semantic_feature), _opt(opacity), _opt(scales), _opt(rotations),
+            float(scale_modifier), _opt(cov3D_precomp), viewmatrices, projmatrices, [float(x) for x in c_x],
+            [float(x) for x in c_y], [float(x) for x in tan_fovx], [float(x) for x in tan_fovy], int(image_height),
+            int(image_width), _opt(sh), int(degree), campos, bool(prefiltered), bool(debug), cm, bool(activate),
+            _windows_arg(windows), _event_handle(feature_ready), cap, plan_state.hint if sync_free else [],
+            _opt(walk_order), _opt(zero_fill), _lib.stream(means3D.device))
+    except RuntimeError as ex:
+        raise _lib.GsplatError(str(ex)) from None
+    NR, color, fmap, depth, alpha, radii, geom, binning, img, NI, layout, hint, fitted = out
     if sync_free:
-        cap_list = plan_state.next_capacity(C)
-        cap = (ctypes.c_int64 * C)(*cap_list)
-        hint = _lib.GsBatchHint(*plan_state.hint)
-        binning = torch.empty(max(1, L_.gs_batch_binning_buffer_bytes(C, cap)), **u8)
-        fits = ctypes.c_int32(0)
-        check(L_.gs_forward_batch(ctypes.byref(g), cams, C, int(bool(prefiltered)), cm, geom.data_ptr(),
-                                  img.data_ptr(), binning.data_ptr(), cap, ctypes.byref(hint), radii.data_ptr(),
-                                  NR, NI, ctypes.byref(fits), *outs, stream),
-              "rasterize_gaussians_batch (sync-free forward)")
-        fitted = bool(fits.value)
-    else:
-        check(L_.gs_forward_plan_batch(ctypes.byref(g), cams, C, int(bool(prefiltered)), int(bool(debug)), cm,
-                                       geom.data_ptr(), img.data_ptr(), radii.data_ptr(), NR, NI, stream),
-              "rasterize_gaussians_batch (preprocess)")
-    layout = list(NI)
-    if fitted:
-        layout = cap_list
-    else:
-        binning = torch.empty(max(1, L_.gs_batch_binning_buffer_bytes(C, NI)), **u8)
-        check(L_.gs_forward_render_batch(ctypes.byref(g), cams, C, int(bool(debug)), cm, geom.data_ptr(),
-                                         binning.data_ptr(), img.data_ptr(), NI, radii.data_ptr(), *outs, stream),
-              "rasterize_gaussians_batch (render)")
-    if sync_free:
-        plan_state.update(list(NI), [hint.valid, hint.p1, hint.q1, hint.p2, hint.max_len, hint.total], fitted,
-                          first=not any(cap_list))
-    del keep
-    return (list(NR), out_color, _user_width(out_feature, 1, inp), out_depth, out_alpha, radii, geom, binning, img,
-            layout)
+        plan_state.update(NI, hint, fitted, first=not any(cap))
+        return (NR, color, fmap, depth, alpha, radii, geom, binning, img, layout)
+    return (NR, color, fmap, depth, alpha, radii, geom, binning, img, NI)
 
 
 def rasterize_gaussians_batch_backward(background, means3D, radii, colors, semantic_feature, scales,
@@ -571,26 +426,6 @@ def rasterize_gaussians_batch_backward(background, means3D, radii, colors, seman
                      scratch_zeroed=scratch_zeroed)
 
 
-def _gradient_outputs(out, exact, P, F, M, dev):
-    """The backward's nine gradient tensors by name: fresh ones, or the
-    caller's `out` -- with `exact` in backward_buffers' shapes (the
-    GradientSink contract), else matched by element count and viewed in those
-    shapes (a gradient bucket's flat views)."""
-    bufs = {}
-    for k, shape in _buffer_shapes(P, F, M).items():
-        t = None if out is None else out.get(k)
-        if t is None:
-            bufs[k] = torch.empty(*shape, dtype=torch.float32, device=dev)
-            continue
-        n = math.prod(shape)
-        fits = tuple(t.shape) == shape if exact else t.numel() == n
-        if not fits or t.dtype != torch.float32 or t.device != dev or not t.is_contiguous():
-            want = f"{shape} tensor" if exact else f"tensor of {n} elements"
-            raise RuntimeError(f"gradient buffer {k} must be a contiguous fp32 {want} on {dev}")
-        bufs[k] = t.view(shape)
-    return bufs
-
-
 def _backward(background, means3D, radii, colors, semantic_feature, scales, rotations, scale_modifier,
               cov3D_precomp, viewmatrices, projmatrices, c_x, c_y, tan_fovx, tan_fovy, dL_dout_color,
               dL_dout_feature, dL_dout_depth, dL_dout_alpha, sh, degree, campos, geomBuffer, num_instances,
@@ -601,7 +436,6 @@ def _backward(background, means3D, radii, colors, semantic_feature, scales, rota
     C = 1 what the single-camera entry point runs).  `exact_out`: `out` holds every gradient
     name in its exact shape (else any subset, by element count);
     `accumulate`: the gradients are ADDED to `out` (GS_FLAG_ACCUMULATE)."""
-    L_ = _lib.load()
     cm = _compat_code(compat)
     if activate and not _present(opacity):
         raise RuntimeError("activate=True needs the raw opacities")
@@ -611,79 +445,19 @@ def _backward(background, means3D, radii, colors, semantic_feature, scales, rota
         odd = _BUFFER_NAMES - out.keys() if exact_out else out.keys() - _BUFFER_NAMES
         if odd:
             raise RuntimeError(f"out: {'missing' if exact_out else 'unknown'} gradient names {sorted(odd)}")
-    nat = _native_mod()
-    C = len(c_x)
-    if _native_serves(nat, means3D):
-        try:
-            return tuple(nat.backward_batch(
-                background, means3D, radii, _opt(colors), _opt(semantic_feature), _opt(scales), _opt(rotations),
-                float(scale_modifier), _opt(cov3D_precomp), viewmatrices, projmatrices, [float(x) for x in c_x],
-                [float(x) for x in c_y], [float(x) for x in tan_fovx], [float(x) for x in tan_fovy],
-                _opt(dL_dout_color), _opt(dL_dout_feature), _opt(dL_dout_depth), _opt(dL_dout_alpha), _opt(sh),
-                int(degree), campos, geomBuffer, [int(x) for x in num_instances], _opt(binningBuffer), imageBuffer,
-                alphas, bool(debug), cm, _opt(grad_mask), None if densify is None else list(densify),
-                _opt(opacity), bool(activate), _windows_arg(windows),
-                [out.get(k, _NO_DEST) for k in _BUFFER_ORDER] if out else [], bool(exact_out), bool(accumulate),
-                _opt(scratch), bool(scratch_zeroed), _lib.stream(means3D.device)))
-        except RuntimeError as ex:
-            raise _lib.GsplatError(str(ex)) from None
-    inp = _Inputs(means3D, colors, semantic_feature, opacity if activate else None, scales, rotations,
-                  scale_modifier, cov3D_precomp, sh, degree)
-    dev, P = inp.device, inp.P
-    f32 = dict(dtype=torch.float32, device=dev)
-    if P == 0:  # answered before any camera argument is looked at
-        return tuple(torch.zeros(*shape, **f32) for shape in _buffer_shapes(0, inp.F_user, inp.M).values())
-    # rasterize_points.cu:160-161 takes H, W from dL_dout_color; an absent
-    # (None / empty) upstream gradient counts as zeros, sized from the alpha image
-    img_ref = dL_dout_color if _present(dL_dout_color) else alphas
-    H, W = img_ref.size(-2), img_ref.size(-1)
-    cams, keep = _camera_batch(dev, background, viewmatrices, projmatrices, campos, c_x, c_y, tan_fovx,
-                               tan_fovy, W, H, windows)
-    g = inp.struct((_lib.GS_FLAG_ACTIVATE if activate else 0) | (_lib.GS_FLAG_ACCUMULATE if accumulate else 0))
-    if grad_mask is not None:
-        gm = grad_mask.to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
-        if gm.numel() != P:
-            raise RuntimeError(f"grad_mask must have {P} elements, got {gm.numel()}")
-        g.grad_mask = gm.data_ptr()
-
-    def img(t, ch, name):  # [C, ch, H, W] of an upstream gradient (channels zero-padded), or None
-        if not _present(t):
-            return None
-        t = _dev(t, dev, name).reshape(C, -1, H, W)
-        if t.size(1) < ch:
-            t = torch.cat([t, torch.zeros(C, ch - t.size(1), H, W, **f32)], 1)
-        return t.contiguous()
-    dLc = img(dL_dout_color, 3, "dL_dout_color")
-    dLd = img(dL_dout_depth, 1, "dL_dout_depth")
-    dLa = img(dL_dout_alpha, 1, "dL_dout_alpha")
-    dLf = img(dL_dout_feature, inp.F, "dL_dout_feature") if inp.F else None
-    alphas_c = _dev(alphas, dev, "alpha")
-    radii_c = radii.to(device=dev, dtype=torch.int32).contiguous()
-    if tuple(radii_c.shape) != (C, P):
-        raise RuntimeError(f"radii must be [C={C}, P={P}]")
-    out = _gradient_outputs(out, exact_out, P, inp.F, inp.M, dev)
-    if densify is not None:
-        for t in densify:
-            if tuple(t.shape) != (P,) or t.dtype != torch.float32 or t.device != dev or not t.is_contiguous():
-                raise RuntimeError(f"densify statistics must be contiguous fp32 ({P},) tensors on {dev}")
-        g.densify_accum, g.densify_denom, g.max_radius = (t.data_ptr() for t in densify)
-    NI = (ctypes.c_int64 * C)(*[int(x) for x in num_instances])
-    nscr = L_.gs_batch_backward_scratch_bytes(P, inp.F, C)
-    if scratch is None:
-        scratch = torch.empty(nscr, dtype=torch.uint8, device=dev)
-    else:
-        if not (scratch.is_contiguous() and scratch.device == dev and scratch.numel() * scratch.element_size() >= nscr):
-            raise RuntimeError(f"scratch must be a contiguous device tensor of {nscr} bytes on {dev}")
-        if scratch_zeroed:
-            g.flags |= _lib.GS_FLAG_SCRATCH_ZEROED
-    stream = _lib.stream(dev)
-    p = lambda t: t.data_ptr() if (t is not None and t.numel()) else None  # noqa: E731
-    check(L_.gs_backward_batch(ctypes.byref(g), cams, C, radii_c.data_ptr(), int(bool(debug)), cm,
-                               geomBuffer.data_ptr(), p(binningBuffer), imageBuffer.data_ptr(), NI,
-                               alphas_c.data_ptr(), p(dLc), p(dLf), p(dLd), p(dLa), scratch.data_ptr(),
-                               *(p(out[k]) if k in ("dsem", "dsh") else out[k].data_ptr() for k in _BUFFER_ORDER),
-                               stream), "rasterize_gaussians_batch_backward")
-    del keep
-    out["dsem"] = _user_width(out["dsem"], 1, inp)
-    return tuple(out[k] for k in _BUFFER_ORDER)
-
+    if _num_points(means3D) == 0:  # answered before any camera argument is looked at
+        return tuple(torch.zeros(*shape, dtype=torch.float32, device=means3D.device)
+                     for shape in _buffer_shapes(0, 0, 0).values())
+    try:
+        return tuple(_native_mod().backward_batch(
+            background, means3D, radii, _opt(colors), _opt(semantic_feature), _opt(scales), _opt(rotations),
+            float(scale_modifier), _opt(cov3D_precomp), viewmatrices, projmatrices, [float(x) for x in c_x],
+            [float(x) for x in c_y], [float(x) for x in tan_fovx], [float(x) for x in tan_fovy],
+            _opt(dL_dout_color), _opt(dL_dout_feature), _opt(dL_dout_depth), _opt(dL_dout_alpha), _opt(sh),
+            int(degree), campos, geomBuffer, [int(x) for x in num_instances], _opt(binningBuffer), imageBuffer,
+            alphas, bool(debug), cm, _opt(grad_mask), None if densify is None else list(densify),
+            _opt(opacity), bool(activate), _windows_arg(windows),
+            [out.get(k, _NO_DEST) for k in _BUFFER_ORDER] if out else [], bool(exact_out), bool(accumulate),
+            _opt(scratch), bool(scratch_zeroed), _lib.stream(means3D.device)))
+    except RuntimeError as ex:
+        raise _lib.GsplatError(str(ex)) from None

@@ -3,9 +3,9 @@ rasterizer, a drop-in for Dynamic3DGaussians' `diff_gaussian_rasterization`.
 
 Layout:
   csrc/           hand-written HIP kernels + the C ABI (include/gsplat_hip.h)
-  build.py        hipcc build of lib/libgsplat_hip.so (in-tree)
-  _lib.py         ctypes binding of the C ABI (fails loudly; no CPU fallback)
-  _C.py           positional mirror of the reference pybind module `_C`
+  build.py        hipcc build of lib/libgsplat_hip.so and of the rasterizer's C++ binding (in-tree)
+  _lib.py         loads the library: ctypes mirrors of the C ABI (fails loudly; no CPU fallback)
+  _C.py           positional mirror of the reference pybind module `_C`, over csrc/gs_torch_binding.cpp
   rasterizer.py   autograd boundary (GaussianRasterizer & friends)
   camera.py       helpers.setup_camera restatement + synthetic camera rig
   scene.py        synthetic scenes for tests and the benchmark

@@ -1,8 +1,12 @@
-"""ctypes binding of libgsplat_hip.so (C ABI: include/gsplat_hip.h).
+"""Loader and ctypes mirrors of libgsplat_hip.so (C ABI: include/gsplat_hip.h).
 
-This is the only way the package reaches the GPU: there is no CPU or PyTorch
-fallback.  If the HIP library is missing or cannot be loaded, every entry point
-raises immediately with the reason.
+The library is the only way the package reaches the GPU: there is no CPU or
+PyTorch fallback.  If it is missing or cannot be loaded, every entry point
+raises immediately with the reason.  The losses, the optimizer, densification
+and the motion warp are called through the prototypes below; the rasterizer's
+forward and backward go through the C++ binding instead (_C.py,
+csrc/gs_torch_binding.cpp), and their prototypes and struct mirrors here serve
+the tests and tools that drive the C ABI directly.
 """
 from __future__ import annotations
 

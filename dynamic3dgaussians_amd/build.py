@@ -50,7 +50,7 @@ VARIANT_FLAGS = {"": [], "stats": ["-DGS_STATS"], "stamps": ["-DGS_STAMPS"],
                  "motion_alt": ["-DGS_MOTION_FWD_PAIR", "-DGS_MOTION_STORE_SUM"],
                  # the resample backward's measured alternative: one plane per step, not four
                  "rs_pb1": ["-DGS_RS_PLANE_BATCH=1"],
-                 "ctl": []}  # the product's flags under a variant's (ctypes) binding: the A/B control
+                 "ctl": []}  # the product's flags under a variant name: the A/B control
 PATCHED = ("exp_nofeat", "exp_noacc", "exp_noatomic", "exp_fwd_nofeatst", "exp_sort_copy", "exp_rot_all", "exp_fwd_row0")
 ARCH = os.environ.get("GSPLAT_OFFLOAD_ARCH", "gfx950")
 
@@ -162,8 +162,12 @@ def build(force: bool = False, verbose: bool = False) -> str:
     return LIB
 
 
+# The C++ binding of `_C` (csrc/gs_torch_binding.cpp): one module per library,
+# named, like LIB / BUILD_DIR, with the variant's suffix.
 NATIVE_SRC = os.path.join(CSRC, "gs_torch_binding.cpp")
-NATIVE = os.path.join(OUT_DIR, "_gs_native.so")
+NATIVE_NAME = f"_gs_native_{VARIANT}" if VARIANT else "_gs_native"
+NATIVE = os.path.join(OUT_DIR, NATIVE_NAME + ".so")
+NATIVE_BUILD_DIR = os.path.join(OUT_DIR, f"native_obj_{VARIANT}" if VARIANT else "native_obj")
 
 
 def native_is_stale() -> bool:
@@ -174,24 +178,22 @@ def native_is_stale() -> bool:
 
 
 def build_native(force: bool = False, verbose: bool = False) -> str:
-    """The C++ fast path of the `_C` binding (csrc/gs_torch_binding.cpp): a
-    torch extension (host code only) linked against libgsplat_hip.so, written
-    to lib/_gs_native.so next to it (rpath $ORIGIN)."""
-    if VARIANT:
-        return ""
+    """The C++ binding of `_C` (csrc/gs_torch_binding.cpp): a torch extension
+    (host code only) linked against this build's library (LIB, by file name),
+    written next to it (rpath $ORIGIN)."""
     if not force and not native_is_stale():
         return NATIVE
     from torch.utils import cpp_extension  # heavy import, only when building
-    bdir = os.path.join(OUT_DIR, "native_obj")
-    os.makedirs(bdir, exist_ok=True)
+    os.makedirs(NATIVE_BUILD_DIR, exist_ok=True)
     os.environ.setdefault("MAX_JOBS", "4")
-    cpp_extension.load(name="_gs_native", sources=[NATIVE_SRC], build_directory=bdir,
+    cpp_extension.load(name=NATIVE_NAME, sources=[NATIVE_SRC], build_directory=NATIVE_BUILD_DIR,
                        extra_include_paths=[INCLUDE], extra_cflags=["-O2"],
                        # rpath $ORIGIN (lib/) and $ORIGIN/.. (the build dir's parent, lib/),
                        # escaped for ninja ($$) and the shell ('')
-                       extra_ldflags=[f"-L{OUT_DIR}", "-lgsplat_hip", "-Wl,-rpath,'$$ORIGIN:$$ORIGIN/..'"],
+                       extra_ldflags=[f"-L{OUT_DIR}", f"-l:{os.path.basename(LIB)}",
+                                      "-Wl,-rpath,'$$ORIGIN:$$ORIGIN/..'"],
                        with_cuda=False, verbose=verbose, is_python_module=True)
-    built = os.path.join(bdir, "_gs_native.so")
+    built = os.path.join(NATIVE_BUILD_DIR, NATIVE_NAME + ".so")
     tmp = NATIVE + ".tmp"
     shutil.copyfile(built, tmp)
     os.replace(tmp, NATIVE)
@@ -204,8 +206,7 @@ def main():
     ap.add_argument("-v", "--verbose", action="store_true")
     args = ap.parse_args()
     print(build(force=args.force, verbose=args.verbose))
-    if not VARIANT:
-        print(build_native(force=args.force, verbose=args.verbose))
+    print(build_native(force=args.force, verbose=args.verbose))
 
 
 if __name__ == "__main__":

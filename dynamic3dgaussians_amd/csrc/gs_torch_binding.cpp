@@ -1,16 +1,16 @@
-// gs_torch_binding.cpp -- native (C++) fast path of the `_C` binding.
+// gs_torch_binding.cpp -- the C++ binding behind `_C`.
 //
 // The reference binds its rasterizer with a C++ torch extension
 // (DGR/rasterize_points.cu:35-246, RasterizeGaussiansCUDA /
 // RasterizeGaussiansBackwardCUDA, DGR/ext.cpp:15-19).  This file is our
-// counterpart on top of the C ABI (include/gsplat_hip.h): the same argument
-// handling as dynamic3dgaussians_amd/_C.py (which remains the documented
-// ctypes binding and the fallback for argument errors), without the Python
-// per-call work -- tensor checks, output allocation, struct packing and the
-// ABI calls are ~0.2 ms of host time per camera in Python, tens of
-// microseconds here.  Built with torch.utils.cpp_extension by build.py into
-// lib/ next to libgsplat_hip.so (found through rpath $ORIGIN).  No device
-// code: every kernel runs through the C ABI.
+// counterpart on top of the C ABI (include/gsplat_hip.h) and the one place a
+// rasterizer call's arguments are handled: tensor checks, output allocation,
+// struct packing and the ABI calls, tens of microseconds of host time per
+// camera.  dynamic3dgaussians_amd/_C.py in front of it keeps the reference's
+// positional signatures, answers an empty scene and host tensors, and does
+// the sync-free plan's bookkeeping.  Built with torch.utils.cpp_extension by
+// build.py into lib/ next to the library it is linked against (found through
+// rpath $ORIGIN).  No device code: every kernel runs through the C ABI.
 #include <torch/extension.h>
 
 #include <stdexcept>
@@ -103,9 +103,9 @@ struct Inputs {
 void* nz(const Tensor& t) { return (t.defined() && t.numel()) ? t.data_ptr() : nullptr; }
 
 // One forward and one backward body over the gs_*_batch entry points, for any
-// number of cameras: the C++ counterpart of _C.rasterize_gaussians_batch and
-// _C._backward.  A single camera (_C.rasterize_gaussians / _backward) is a
-// batch of one, wrapped and unwrapped in Python.  The forward's one host
+// number of cameras, called by _C.rasterize_gaussians_batch and _C._backward.
+// A single camera (_C.rasterize_gaussians / _backward) is a batch of one,
+// wrapped and unwrapped in Python.  The forward's one host
 // round trip (the plan header) sits between the two ABI calls, so the host
 // work around it is on the step's critical path.
 
@@ -370,7 +370,7 @@ std::vector<Tensor> backward_batch(
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
-  m.doc() = "native fast path of dynamic3dgaussians_amd._C (C++ over the gsplat_hip C ABI)";
+  m.doc() = "the binding of dynamic3dgaussians_amd._C (C++ over the gsplat_hip C ABI)";
   m.def("abi_version", []() { return gs_version(); });
   m.def("forward_batch", &forward_batch);
   m.def("backward_batch", &backward_batch);

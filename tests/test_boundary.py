@@ -10,6 +10,7 @@ import json
 import os
 import re
 import subprocess
+import sys
 
 import pytest
 import torch
@@ -42,6 +43,23 @@ def test_library_exports_every_declared_symbol():
                          text=True).stdout
     exported = set(re.findall(r" T (gs_[a-z_0-9]+)", out))
     assert set(names) <= exported
+
+
+def test_binding_module_follows_the_build_variant():
+    """GSPLAT_VARIANT names the binding module as it names the library: file,
+    module name, and the library its staleness is judged against (path logic)."""
+    code = ("import importlib.util as u, os, sys\n"
+            "s = u.spec_from_file_location('b', sys.argv[1]); b = u.module_from_spec(s); s.loader.exec_module(b)\n"
+            "os.path.getmtime = lambda f: 2.0 if f == b.LIB else 1.0\n"
+            "os.path.exists = lambda f: True\n"
+            "print(b.NATIVE_NAME, os.path.relpath(b.NATIVE, b.OUT_DIR), os.path.relpath(b.LIB, b.OUT_DIR),\n"
+            "      os.path.basename(b.NATIVE_BUILD_DIR), b.native_is_stale())\n")
+    build_py = os.path.join(REPO, "dynamic3dgaussians_amd", "build.py")
+    for variant, want in (("stats", "_gs_native_stats _gs_native_stats.so libgsplat_hip_stats.so native_obj_stats True"),
+                          ("", "_gs_native _gs_native.so libgsplat_hip.so native_obj True")):
+        out = subprocess.run([sys.executable, "-c", code, build_py], capture_output=True, text=True, check=True,
+                             env={**os.environ, "GSPLAT_VARIANT": variant}).stdout
+        assert out.split() == want.split(), (variant, out)
 
 
 def test_abi_version_and_sizes():

@@ -52,9 +52,8 @@ def make_means(P):
     return (torch.randn(P, 3, device=DEV, generator=g) * torch.tensor([2.0, 1.0, 0.5], device=DEV)).contiguous()
 
 
-@pytest.mark.parametrize("binding", ["native", "ctypes"])
-@pytest.mark.parametrize("sync_free", [True, False])
-def test_spatial_walk_gives_the_id_order_outputs(binding, sync_free, P=20000, W=208, H=160, F=32, C=5):
+@pytest.mark.parametrize("sync_free", [True, False], ids=["True-native", "False-native"])  # the cases' ids
+def test_spatial_walk_gives_the_id_order_outputs(sync_free, P=20000, W=208, H=160, F=32, C=5):
     src = _scene(P, F, seed=4)
     rig = camera_rig(C, W, H)
     gx, gy = (W + 15) // 16, (H + 15) // 16
@@ -62,17 +61,12 @@ def test_spatial_walk_gives_the_id_order_outputs(binding, sync_free, P=20000, W=
     ups = _ups(C, F, W, H)
     lab = torch.ones(P, device=DEV)
     assert _C.native_loaded(), "the native binding did not load"
-    keep = _C._native
-    try:
-        _C._native = keep if binding == "native" else None
-        ref_o, ref_g = _run(GaussianRasterizerBatch(sets, sync_free=sync_free), src, ups, lab)
-        ras = GaussianRasterizerBatch(sets, sync_free=sync_free, spatial_order=True, order_refresh=2)
-        for _ in range(3):  # the order computed, reused, recomputed
-            o, g = _run(ras, src, ups, lab)
-            _same(o, ref_o, g, ref_g)
-        assert ras._walk is not None and ras._walk.numel() == P
-    finally:
-        _C._native = keep
+    ref_o, ref_g = _run(GaussianRasterizerBatch(sets, sync_free=sync_free), src, ups, lab)
+    ras = GaussianRasterizerBatch(sets, sync_free=sync_free, spatial_order=True, order_refresh=2)
+    for _ in range(3):  # the order computed, reused, recomputed
+        o, g = _run(ras, src, ups, lab)
+        _same(o, ref_o, g, ref_g)
+    assert ras._walk is not None and ras._walk.numel() == P
 
 
 def test_any_permutation_gives_the_id_order_outputs(P=15000, W=160, H=128, F=32, C=3):

@@ -11,7 +11,10 @@ two-phase plan -> render (sync_free=False; the sync-free forward's first call
 renders every camera empty and retries, which would add a launch of no work
 to the counts -- tools/pmc_*.py refuse such files).  --sync-free runs the
 sync-free forward after one warm call, for timing and stamps only (the warm
-call's launches would be counted too).
+call's launches would be counted too).  --stamps needs a stamps build
+(GSPLAT_VARIANT=stamps python -m dynamic3dgaussians_amd.build, then the same
+variable here): its library and its binding module, lib/_gs_native_stamps.so,
+which serves the calls as the product's module serves the product's.
 """
 from __future__ import annotations
 

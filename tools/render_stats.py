@@ -4,6 +4,10 @@
     GSPLAT_VARIANT=stats python -m dynamic3dgaussians_amd.build --force   # here
     python tools/render_stats.py --features 32 --cams 2                  # on the box
 
+The build line writes the variant's library and its binding module
+(lib/libgsplat_hip_stats.so, lib/_gs_native_stats.so); the calls go through
+that module, as the product's go through its own.
+
 Counters (per camera): chunks, records gathered, strip survivors, inner-loop
 iterations, iterations with >=1 active lane, active lanes -- forward and
 backward -- plus waves and list lengths.
