@@ -508,6 +508,256 @@ void or_render_bwd(int W, int H, const uint32_t *ranges,
   free(acc_f); free(last_f); free(dlf);
 }
 
+/* ------------------------------------------------- fp64 replay of the blend
+ *
+ * Double-precision twins of or_render_fwd / or_render_bwd: the same walk over
+ * the same fp32 records and lists, the same quirks (Q1, Q4, Q5, the bg term),
+ * but double arithmetic with libm exp, and every decision (power > 0,
+ * alpha < 1/255, T(1-alpha) < 1e-4) taken in double against the fp32
+ * thresholds' exact values.  Next to every sum they return its ABSOLUTE sum
+ * (every leaf product replaced by its magnitude): the scale fp32 rounding
+ * error of that sum is proportional to, whatever the summation order.
+ *
+ * A (pixel, Gaussian) pair is UNDECIDED when a decision lies closer to its
+ * threshold than fp32 evaluation can resolve (u = 2^-24, `margin` = the one
+ * margin factor, oracle.MARGIN_FACTOR):
+ *   delta = margin*u*(1 + |a dx^2/2| + |c dy^2/2| + |b dx dy|)
+ *   bit 0: |255 op exp(power) - 1| <= delta
+ *   bit 1: |power| <= delta
+ *   bit 2: |T(1-alpha)/1e-4 - 1| <= u*(margin + 2k) + sum_{j<=k} delta_j alpha_j/(1-alpha_j)
+ *          (k = the pair's 1-based position in the list, j over blended pairs)
+ * Visited = up to and including the stopping pair. */
+
+#define R64_U 5.9604644775390625e-08 /* 2^-24 */
+
+typedef struct {
+  double power, G, alpha, delta;
+  int skip; /* 1: power > 0, 2: alpha < 1/255 */
+  uint8_t flag;
+  double closeness; /* min over this pair's decisions of distance / tolerance */
+} pair64_t;
+
+static void pair64(const float *means2D, const float *conic_opacity, uint32_t g,
+                   double pfx, double pfy, double margin, pair64_t *p) {
+  const double dx = (double)means2D[2 * g] - pfx, dy = (double)means2D[2 * g + 1] - pfy;
+  const float *co = conic_opacity + 4 * g;
+  const double ta = 0.5 * (double)co[0] * dx * dx, tc = 0.5 * (double)co[2] * dy * dy;
+  const double tb = (double)co[1] * dx * dy;
+  p->power = -(ta + tc) - tb;
+  p->delta = margin * R64_U * (1.0 + fabs(ta) + fabs(tc) + fabs(tb));
+  p->flag = 0;
+  p->skip = 0;
+  p->G = 0; p->alpha = 0;
+  p->closeness = fabs(p->power) / p->delta;
+  if (fabs(p->power) <= p->delta) p->flag |= 2;
+  if (p->power > 0.0) { p->skip = 1; return; }
+  p->G = exp(p->power);
+  const double oa = (double)co[3] * p->G;
+  const double c1 = fabs(255.0 * oa - 1.0) / p->delta;
+  if (c1 < p->closeness) p->closeness = c1;
+  if (c1 <= 1.0) p->flag |= 1;
+  p->alpha = fmin((double)0.99f, oa);
+  if (p->alpha < (double)(1.0f / 255.0f)) p->skip = 2;
+}
+
+/* Forward replay.  Per pixel (pixel-major, C = 5 + F columns: colour 0..2,
+ * depth, alpha, feature 0..F-1): val and its absolute sum A; n_blend (number
+ * of blended contributors), last_pos (n_contrib: 1-based list position of the
+ * last contributor, 0 if none), last_id (its Gaussian id, -1 if none), flag
+ * (OR of the undecided bits over the visited pairs), closeness (min over the
+ * visited pairs' decisions of distance / tolerance; > 1 everywhere means
+ * decided).  gflag[P] (caller-zeroed) ORs the bits per owning Gaussian. */
+void or_render_fwd64(int W, int H, const uint32_t *ranges,
+                     const uint32_t *point_list, const float *means2D,
+                     const float *colors, const float *feats, int F,
+                     const float *depths, const float *conic_opacity,
+                     const float *bg, int compat, double margin, double *val,
+                     double *A, int32_t *n_blend, uint32_t *last_pos,
+                     int32_t *last_id, uint8_t *flag, double *closeness,
+                     uint8_t *gflag) {
+  const int gx = (W + TILE - 1) / TILE;
+  const int C = 5 + F;
+  for (int py = 0; py < H; ++py)
+    for (int px = 0; px < W; ++px) {
+      const int tile = (py / TILE) * gx + px / TILE;
+      const uint32_t r0 = ranges[2 * tile], r1 = ranges[2 * tile + 1];
+      const size_t pix = (size_t)py * W + px;
+      double *v = val + pix * C, *a = A + pix * C;
+      for (int c = 0; c < C; ++c) { v[c] = 0; a[c] = 0; }
+      double T = 1.0, relsum = 0.0, close = INFINITY;
+      uint32_t contributor = 0, last = 0;
+      int32_t lid = -1, nb = 0;
+      uint8_t fl = 0;
+      for (uint32_t i = r0; i < r1; ++i) {
+        contributor++;
+        const uint32_t g = point_list[i];
+        pair64_t p;
+        pair64(means2D, conic_opacity, g, (double)px, (double)py, margin, &p);
+        fl |= p.flag; gflag[g] |= p.flag;
+        if (p.closeness < close) close = p.closeness;
+        if (p.skip) continue;
+        const double test_T = T * (1.0 - p.alpha);
+        relsum += p.delta * p.alpha / (1.0 - p.alpha);
+        const double tol = R64_U * (margin + 2.0 * (double)contributor) + relsum;
+        const double cs = fabs(test_T / (double)0.0001f - 1.0) / tol;
+        if (cs < close) close = cs;
+        if (cs <= 1.0) { fl |= 4; gflag[g] |= 4; }
+        if (test_T < (double)0.0001f) break;
+        const double w = p.alpha * T;
+        for (int ch = 0; ch < 3; ++ch) {
+          v[ch] += (double)colors[3 * g + ch] * w;
+          a[ch] += fabs((double)colors[3 * g + ch]) * w;
+        }
+        v[3] += (double)depths[g] * w;
+        a[3] += fabs((double)depths[g]) * w;
+        for (int ch = 0; ch < F; ++ch) {
+          v[5 + ch] += (double)feats[(size_t)g * F + ch] * w;
+          a[5 + ch] += fabs((double)feats[(size_t)g * F + ch]) * w;
+        }
+        T = test_T;
+        last = contributor;
+        lid = (int32_t)g;
+        nb++;
+      }
+      for (int ch = 0; ch < 3; ++ch) {
+        v[ch] += T * (double)bg[ch];
+        a[ch] += T * fabs((double)bg[ch]);
+      }
+      for (int ch = 0; ch < F && ch < 3; ++ch)
+        if (compat == GS_COMPAT_REFERENCE) { /* Q4 */
+          v[5 + ch] += T * (double)bg[ch];
+          a[5 + ch] += T * fabs((double)bg[ch]);
+        }
+      if (compat != GS_COMPAT_REFERENCE) { v[4] = 1.0 - T; a[4] = 1.0 + T; } /* Q1 */
+      n_blend[pix] = nb; last_pos[pix] = last; last_id[pix] = lid;
+      flag[pix] = fl; closeness[pix] = close;
+    }
+}
+
+/* Backward replay.  `alphas` is the backward's input image (T_final =
+ * 1 - alphas, as in or_render_bwd; zeros in reference mode, Q1), the fp32
+ * image widened to double, or an fp64 one for fp64-level comparisons; the last
+ * contributor is found by the replay's own forward walk.  Per Gaussian
+ * (G = 10 + F columns: dmean2D x y, dconic a b c, dopacity, dcolors 0..2,
+ * ddepth, dsemantic 0..F-1), accumulated into caller-zeroed arrays: sum and
+ * absolute sum. */
+void or_render_bwd64(int W, int H, const uint32_t *ranges,
+                     const uint32_t *point_list, const float *bg,
+                     const float *means2D, const float *conic_opacity,
+                     const float *colors, const float *feats, int F,
+                     const float *depths, const double *alphas,
+                     const float *dL_dpix, const float *dL_dfeat,
+                     const float *dL_ddepth_pix, const float *dL_dalpha_pix,
+                     int compat, double *sum, double *asum) {
+  const int gx = (W + TILE - 1) / TILE;
+  const size_t HW = (size_t)H * W;
+  const int NG = 10 + F;
+  const double ddelx_dx = 0.5 * W, ddely_dy = 0.5 * H;
+  const int Fa = F > 0 ? F : 1;
+  double *acc_f = (double *)malloc(sizeof(double) * Fa * 4);
+  double *acc_fa = acc_f + Fa, *last_f = acc_f + 2 * Fa, *dlf = acc_f + 3 * Fa;
+  for (int py = 0; py < H; ++py)
+    for (int px = 0; px < W; ++px) {
+      const int tile = (py / TILE) * gx + px / TILE;
+      const uint32_t r0 = ranges[2 * tile], r1 = ranges[2 * tile + 1];
+      const size_t pix = (size_t)py * W + px;
+      /* the replay's own forward decisions: the last contributor */
+      uint32_t last_contrib = 0;
+      {
+        double Tf = 1.0;
+        uint32_t contributor = 0;
+        for (uint32_t i = r0; i < r1; ++i) {
+          contributor++;
+          pair64_t p;
+          pair64(means2D, conic_opacity, point_list[i], (double)px, (double)py, 1.0, &p);
+          if (p.skip) continue;
+          const double test_T = Tf * (1.0 - p.alpha);
+          if (test_T < (double)0.0001f) break;
+          Tf = test_T;
+          last_contrib = contributor;
+        }
+      }
+      const double T_final = 1.0 - alphas[pix];
+      double T = T_final;
+      double acc_rec[3] = {0, 0, 0}, acc_reca[3] = {0, 0, 0}, last_color[3] = {0, 0, 0}, dLp[3];
+      double acc_depth = 0, acc_deptha = 0, last_depth = 0, acc_alpha = 0, last_alpha = 0;
+      for (int ch = 0; ch < 3; ++ch) dLp[ch] = (double)dL_dpix[ch * HW + pix];
+      for (int ch = 0; ch < F; ++ch) {
+        acc_f[ch] = 0; acc_fa[ch] = 0; last_f[ch] = 0; dlf[ch] = (double)dL_dfeat[ch * HW + pix];
+      }
+      const double dLd = (double)dL_ddepth_pix[pix], dLa = (double)dL_dalpha_pix[pix];
+      double bg_dot = 0, bg_abs = 0;
+      for (int ch = 0; ch < 3; ++ch) {
+        bg_dot += (double)bg[ch] * dLp[ch];
+        bg_abs += fabs((double)bg[ch] * dLp[ch]);
+      }
+      for (uint32_t k = r1 - r0; k-- > 0;) {
+        if (k >= last_contrib) continue;
+        const uint32_t g = point_list[r0 + k];
+        pair64_t p;
+        pair64(means2D, conic_opacity, g, (double)px, (double)py, 1.0, &p);
+        if (p.skip) continue;
+        const float *co = conic_opacity + 4 * g;
+        const double dx = (double)means2D[2 * g] - (double)px, dy = (double)means2D[2 * g + 1] - (double)py;
+        const double alpha = p.alpha, G = p.G;
+        double *s = sum + (size_t)g * NG, *a = asum + (size_t)g * NG;
+        T = T / (1.0 - alpha);
+        const double dchannel = alpha * T;
+        double S = 0, Sa = 0;
+        for (int ch = 0; ch < 3; ++ch) {
+          const double c = (double)colors[3 * g + ch];
+          acc_rec[ch] = last_alpha * last_color[ch] + (1.0 - last_alpha) * acc_rec[ch];
+          acc_reca[ch] = last_alpha * fabs(last_color[ch]) + (1.0 - last_alpha) * acc_reca[ch];
+          last_color[ch] = c;
+          S += (c - acc_rec[ch]) * dLp[ch];
+          Sa += (fabs(c) + acc_reca[ch]) * fabs(dLp[ch]);
+          s[6 + ch] += dchannel * dLp[ch];
+          a[6 + ch] += fabs(dchannel * dLp[ch]);
+        }
+        const double cd = (double)depths[g];
+        acc_depth = last_alpha * last_depth + (1.0 - last_alpha) * acc_depth;
+        acc_deptha = last_alpha * fabs(last_depth) + (1.0 - last_alpha) * acc_deptha;
+        last_depth = cd;
+        S += (cd - acc_depth) * dLd;
+        Sa += (fabs(cd) + acc_deptha) * fabs(dLd);
+        for (int ch = 0; ch < F; ++ch) {
+          const double f = (double)feats[(size_t)g * F + ch];
+          if (compat != GS_COMPAT_REFERENCE) { /* Q5: dead in reference mode */
+            acc_f[ch] = last_alpha * last_f[ch] + (1.0 - last_alpha) * acc_f[ch];
+            acc_fa[ch] = last_alpha * fabs(last_f[ch]) + (1.0 - last_alpha) * acc_fa[ch];
+            last_f[ch] = f;
+            S += (f - acc_f[ch]) * dlf[ch];
+            Sa += (fabs(f) + acc_fa[ch]) * fabs(dlf[ch]);
+          }
+          s[10 + ch] += dchannel * dlf[ch];
+          a[10 + ch] += fabs(dchannel * dlf[ch]);
+        }
+        s[9] += dchannel * dLd;
+        a[9] += fabs(dchannel * dLd);
+        acc_alpha = last_alpha + (1.0 - last_alpha) * acc_alpha;
+        S += (1.0 - acc_alpha) * dLa;
+        Sa += (1.0 + acc_alpha) * fabs(dLa);
+        last_alpha = alpha;
+        const double bgf = T_final / (1.0 - alpha);
+        const double dopa = S * T - bgf * bg_dot;
+        const double dopa_a = Sa * T + bgf * bg_abs;
+        const double op = (double)co[3];
+        const double dG = op * dopa, dG_a = fabs(op) * dopa_a;
+        const double gdx = G * dx, gdy = G * dy;
+        const double ca = (double)co[0], cb = (double)co[1], cc = (double)co[2];
+        s[0] += dG * (-gdx * ca - gdy * cb) * ddelx_dx;
+        a[0] += dG_a * (fabs(gdx * ca) + fabs(gdy * cb)) * ddelx_dx;
+        s[1] += dG * (-gdy * cc - gdx * cb) * ddely_dy;
+        a[1] += dG_a * (fabs(gdy * cc) + fabs(gdx * cb)) * ddely_dy;
+        s[2] += -0.5 * gdx * dx * dG;  a[2] += 0.5 * fabs(gdx * dx) * dG_a;
+        s[3] += -0.5 * gdx * dy * dG;  a[3] += 0.5 * fabs(gdx * dy) * dG_a;
+        s[4] += -0.5 * gdy * dy * dG;  a[4] += 0.5 * fabs(gdy * dy) * dG_a;
+        s[5] += G * dopa;              a[5] += G * dopa_a;
+      }
+    }
+  free(acc_f);
+}
+
 /* computeColorFromSH (backward), CR/backward.cu:20-139. */
 static void sh_bwd(int g, int deg, int M, const float *mean, const float *campos,
                    const float *shs, const uint8_t *clamped, const float *dcolor,

@@ -27,6 +27,11 @@ LIB_PATH = os.path.join(HERE, "build", "libgs_oracle.so")
 
 COMPAT = {"reference": 0, "fixed": 1}
 TILE = 16
+# The one margin factor of the fp64 replay's "undecided" test (gs_oracle.c,
+# "fp64 replay of the blend"): a decision closer to its threshold than
+# MARGIN_FACTOR * 2^-24 * (1 + the power's absolute sum) counts as undecided.
+MARGIN_FACTOR = 8.0
+U32 = 2.0 ** -24
 
 _f = ctypes.POINTER(ctypes.c_float)
 _i = ctypes.POINTER(ctypes.c_int)
@@ -34,6 +39,8 @@ _u32 = ctypes.POINTER(ctypes.c_uint32)
 _u64 = ctypes.POINTER(ctypes.c_uint64)
 _u8 = ctypes.POINTER(ctypes.c_uint8)
 _I, _F = ctypes.c_int, ctypes.c_float
+_d = ctypes.POINTER(ctypes.c_double)
+_D = ctypes.c_double
 
 _lib = None
 
@@ -63,6 +70,12 @@ def lib():
         L.or_render_bwd.argtypes = [_I, _I, _u32, _u32, _f, _f, _f, _f, _f, _I, _f, _f, _u32,
                                     _f, _f, _f, _f, _I, _f, _f, _f, _f, _f, _f]
         L.or_render_bwd.restype = None
+        L.or_render_fwd64.argtypes = [_I, _I, _u32, _u32, _f, _f, _f, _I, _f, _f, _f, _I, _D,
+                                      _d, _d, _i, _u32, _i, _u8, _d, _u8]
+        L.or_render_fwd64.restype = None
+        L.or_render_bwd64.argtypes = [_I, _I, _u32, _u32, _f, _f, _f, _f, _f, _I, _f, _d,
+                                      _f, _f, _f, _f, _I, _d, _d]
+        L.or_render_bwd64.restype = None
         L.or_set_pixel_order.argtypes = [_u32, ctypes.c_int64]
         L.or_set_pixel_order.restype = None
         L.or_preprocess_bwd.argtypes = [_I, _I, _I, _f, _i, _f, _u8, _f, _f, _F, _f, _f, _f,
@@ -263,3 +276,113 @@ def rasterize_gaussians_backward(bg, means3D, radii, colors, semantic_feature, s
                          _p(out["dscales"]), _p(out["drot"]))
     state.dconic, state.ddepth = dconic, ddepth
     return tuple(out.values())
+
+
+# ------------------------------------------------------------ fp64 replay
+
+FWD64_COLS = 5   # colour 0..2, depth, alpha, then F feature columns
+BWD64_COLS = 10  # dmean2D x y, dconic a b c, dopacity, dcolors 0..2, ddepth, then F dsemantic columns
+
+
+def _records(rec):
+    """The fp32 per-Gaussian records and tile lists the blend reads, from an
+    OracleState or from the dict tests' export_state returns."""
+    get = (lambda k: rec[k]) if isinstance(rec, dict) else (lambda k: getattr(rec, k))
+    return (np.ascontiguousarray(get("ranges"), np.uint32).reshape(-1),
+            np.ascontiguousarray(get("point_list"), np.uint32).reshape(-1),
+            _np(get("means2D")), _np(get("depths")), _np(get("conic_opacity")))
+
+
+def render_forward64(rec, W, H, colors, feats, bg, compat="reference", margin=MARGIN_FACTOR):
+    """fp64 replay of the forward blend (or_render_fwd64) over the records and
+    lists of `rec` (the oracle's state, or the GPU's exported -- pruned --
+    lists).  `colors` [P,3] are the blended colours (precomputed, or the
+    preprocess's SH rgb), `feats` [P,F] or None.  Returns a dict of float64
+    images color[3,H,W], feature[F,H,W], depth[1,H,W], alpha[1,H,W], their
+    absolute sums A_color ..., and per pixel n (blended contributors),
+    last_pos (n_contrib), last_id (Gaussian id or -1), flag (undecided bits),
+    closeness (min distance / tolerance over the visited decisions), plus
+    gflag[P] (the bits per owning Gaussian)."""
+    ranges, plist, m2, dep, co = _records(rec)
+    colors, feats, bgv = _np(colors), _np(feats), _np(bg)
+    P = m2.shape[0]
+    F = 0 if feats is None else int(np.prod(feats.shape[1:]))
+    C = FWD64_COLS + F
+    HW = H * W
+    val, A = np.zeros((HW, C)), np.zeros((HW, C))
+    n, last_id = np.zeros(HW, np.int32), np.zeros(HW, np.int32)
+    last_pos, flag = np.zeros(HW, np.uint32), np.zeros(HW, np.uint8)
+    close, gflag = np.zeros(HW), np.zeros(P, np.uint8)
+    if len(plist) == 0:
+        plist = np.zeros(1, np.uint32)
+    lib().or_render_fwd64(W, H, _p(ranges, _u32), _p(plist, _u32), _p(m2), _p(colors), _p(feats), F,
+                          _p(dep), _p(co), _p(bgv), COMPAT[compat], float(margin), _p(val, _d), _p(A, _d),
+                          _p(n, _i), _p(last_pos, _u32), _p(last_id, _i), _p(flag, _u8), _p(close, _d),
+                          _p(gflag, _u8))
+    img = lambda a, lo, hi: np.ascontiguousarray(a[:, lo:hi].T).reshape(hi - lo, H, W)  # noqa: E731
+    out = dict(n=n, last_pos=last_pos, last_id=last_id, flag=flag, closeness=close, gflag=gflag)
+    for name, lo, hi in (("color", 0, 3), ("depth", 3, 4), ("alpha", 4, 5), ("feature", 5, C)):
+        out[name], out["A_" + name] = img(val, lo, hi), img(A, lo, hi)
+    return out
+
+
+def render_backward64(rec, W, H, colors, feats, bg, alpha, grads, compat="reference"):
+    """fp64 replay of the blend backward (or_render_bwd64).  `alpha` is the
+    backward's input image (the forward's fp32 alpha output, widened to
+    float64 here; a float64 image is taken as it is), `grads` the four
+    upstream images (dcolor, dfeature, ddepth, dalpha).  Returns per Gaussian
+    the float64 sums dmean2D[P,2], dconic[P,3], dopacity[P], dcolors[P,3],
+    ddepth[P], dsemantic[P,F] and their absolute sums under "A_" + name."""
+    ranges, plist, m2, dep, co = _records(rec)
+    colors, feats, bgv = _np(colors), _np(feats), _np(bg)
+    P = m2.shape[0]
+    F = 0 if feats is None else int(np.prod(feats.shape[1:]))
+    G = BWD64_COLS + F
+    dc, df, dd, da = (_np(g) for g in grads)
+    if df is None:
+        df = np.zeros((max(F, 1), H, W), np.float32)
+    s, a = np.zeros((P, G)), np.zeros((P, G))
+    if len(plist) == 0:
+        plist = np.zeros(1, np.uint32)
+    lib().or_render_bwd64(W, H, _p(ranges, _u32), _p(plist, _u32), _p(bgv), _p(m2), _p(co), _p(colors),
+                          _p(feats), F, _p(dep), _p(_np(alpha, np.float64), _d), _p(dc), _p(df), _p(dd), _p(da),
+                          COMPAT[compat], _p(s, _d), _p(a, _d))
+    out = {}
+    for name, lo, hi in (("dmean2D", 0, 2), ("dconic", 2, 5), ("dopacity", 5, 6), ("dcolors", 6, 9),
+                         ("ddepth", 9, 10), ("dsemantic", 10, G)):
+        out[name], out["A_" + name] = np.ascontiguousarray(s[:, lo:hi]), np.ascontiguousarray(a[:, lo:hi])
+    for k in ("dopacity", "ddepth", "A_dopacity", "A_ddepth"):
+        out[k] = out[k].reshape(P)
+    return out
+
+
+def preprocess_backward(means3D, radii, sh, degree, scales, rotations, scale_modifier, cov3D_precomp,
+                        viewmatrix, projmatrix, c_x, c_y, tan_fovx, tan_fovy, campos, image_width,
+                        image_height, state, dmean2D, dconic, dcolor, ddepth, compat="reference"):
+    """or_preprocess_bwd on its own: the per-Gaussian upstream sums dmean2D
+    [P,2], dconic [P,3] (a, b, c), dcolor [P,3] and ddepth [P] (rounded to
+    fp32) -> dict dmeans3D, dcov3D, dsh, dscales, drotations.  Camera scalars
+    in the C++ positional order, as rasterize_gaussians_backward takes them."""
+    means3D = _np(means3D)
+    P = means3D.shape[0]
+    sh = _np(sh)
+    M = 0 if sh is None else sh.shape[1]
+    d2 = np.zeros((P, 3), np.float32)
+    d2[:, :2] = np.asarray(dmean2D).reshape(P, 2)
+    dco = np.zeros((P, 4), np.float32)
+    dco[:, [0, 1, 3]] = np.asarray(dconic).reshape(P, 3)
+    dcol = np.ascontiguousarray(np.asarray(dcolor, np.float32).reshape(P, 3))
+    ddep = np.ascontiguousarray(np.asarray(ddepth, np.float32).reshape(P))
+    out = dict(dmeans3D=np.zeros((P, 3), np.float32), dcov3D=np.zeros((P, 6), np.float32),
+               dsh=np.zeros((P, M, 3), np.float32), dscales=np.zeros((P, 3), np.float32),
+               drotations=np.zeros((P, 4), np.float32))
+    cov_pre = _np(cov3D_precomp)
+    cov = cov_pre if cov_pre is not None else state.cov3D
+    lib().or_preprocess_bwd(P, int(degree), M, _p(means3D), _p(_np(radii, np.int32), _i), _p(sh),
+                            _p(state.clamped, _u8), _p(_np(scales)), _p(_np(rotations)),
+                            float(scale_modifier), _p(cov), _p(_np(viewmatrix)), _p(_np(projmatrix)),
+                            int(image_width), int(image_height), float(c_x), float(c_y), float(tan_fovx),
+                            float(tan_fovy), _p(_np(campos)), _p(d2), _p(dco), _p(dcol), _p(ddep),
+                            COMPAT[compat], _p(out["dmeans3D"]), _p(out["dcov3D"]), _p(out["dsh"]),
+                            _p(out["dscales"]), _p(out["drotations"]))
+    return out

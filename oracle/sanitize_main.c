@@ -5,7 +5,8 @@
  * first finding aborts) over
  *   - the C oracle's whole forward and backward chain (or_preprocess ->
  *     or_binning -> or_render_fwd -> or_render_bwd -> or_preprocess_bwd,
- *     or_mark_visible, or_higher_msb, or_set_pixel_order) on seeded scenes:
+ *     or_mark_visible, or_higher_msb, or_set_pixel_order, and the fp64 replay
+ *     or_render_fwd64 / or_render_bwd64 over the same lists) on seeded scenes:
  *     SH degrees 0 / 3 or precomputed colours, F = 0 / 32, both compat modes,
  *     an off-centre principal point, Gaussians on and beyond the image edges;
  *   - the library's host validators (dynamic3dgaussians_amd/csrc/gs_host.cpp:
@@ -51,6 +52,16 @@ void or_preprocess_bwd(int P, int D, int M, const float *means3D, const int *rad
                        float tan_fovx, float tan_fovy, const float *campos, const float *dmean2D, const float *dconic,
                        const float *dcolor, const float *ddepth, int compat, float *dmean3D, float *dcov3D,
                        float *dsh, float *dscale, float *drot);
+
+void or_render_fwd64(int W, int H, const uint32_t *ranges, const uint32_t *point_list, const float *means2D,
+                     const float *colors, const float *feats, int F, const float *depths,
+                     const float *conic_opacity, const float *bg, int compat, double margin, double *val, double *A,
+                     int32_t *n_blend, uint32_t *last_pos, int32_t *last_id, uint8_t *flag, double *closeness,
+                     uint8_t *gflag);
+void or_render_bwd64(int W, int H, const uint32_t *ranges, const uint32_t *point_list, const float *bg,
+                     const float *means2D, const float *conic_opacity, const float *colors, const float *feats,
+                     int F, const float *depths, const double *alphas, const float *dL_dpix, const float *dL_dfeat,
+                     const float *dL_ddepth_pix, const float *dL_dalpha_pix, int compat, double *sum, double *asum);
 
 static uint64_t g_rng = 88172645463325252ull;
 static float urand(void) { /* xorshift64, [0, 1) */
@@ -240,6 +251,29 @@ static void run_case(int P, int W, int H, int D, int F, int compat, int precomp,
     free(dm3); free(dc3); free(dsh); free(dsc); free(drot);
   }
   or_set_pixel_order(NULL, 0);
+  { /* the fp64 replay of the blend over the same records and lists */
+    double *val = xcalloc(HW * (5 + F), 8), *A = xcalloc(HW * (5 + F), 8), *cl = xcalloc(HW, 8), *a64 = xcalloc(HW, 8);
+    int32_t *nb = xcalloc(HW, 4), *lid = xcalloc(HW, 4);
+    uint32_t *lpos = xcalloc(HW, 4);
+    uint8_t *fl = xcalloc(HW, 1), *gfl = xcalloc(P, 1);
+    or_render_fwd64(W, H, ranges, plist, m2, colour_src, F ? feats : NULL, F, depths, conic, bg, compat, 8.0, val, A,
+                    nb, lpos, lid, fl, cl, gfl);
+    size_t same = 0;
+    for (size_t i = 0; i < HW; ++i) {
+      same += lpos[i] == ncon[i];
+      a64[i] = (double)oa[i];
+    }
+    EXPECT(same >= HW - HW / 100, "replay's last contributor equals the oracle's at %zu of %zu pixels", same, HW);
+    double *s64 = xcalloc((size_t)P * (10 + F), 8), *as64 = xcalloc((size_t)P * (10 + F), 8);
+    or_render_bwd64(W, H, ranges, plist, bg, m2, conic, colour_src, F ? feats : NULL, F, depths, a64, dLc,
+                    F ? dLf : NULL, dLd, dLa, compat, s64, as64);
+    for (size_t i = 0; i < (size_t)P * (10 + F); ++i)
+      if (!(fabs(s64[i]) <= as64[i] * (1 + 1e-12))) {
+        EXPECT(0, "replay sum %g exceeds its absolute sum %g", s64[i], as64[i]);
+        break;
+      }
+    free(val); free(A); free(cl); free(a64); free(nb); free(lid); free(lpos); free(fl); free(gfl); free(s64); free(as64);
+  }
   printf("case P=%d %dx%d D=%d F=%d compat=%d precomp=%d: L=%lld visible=%d\n", P, W, H, D, F, compat, precomp,
          (long long)L, visible);
   free(means); free(scales); free(rots); free(opac); free(cols); free(feats); free(shs); free(present);

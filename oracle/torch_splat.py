@@ -8,8 +8,9 @@ and the per-pixel front-to-back blend (CR/forward.cu:330-380) -- as dense
 float64 tensor algebra over every (pixel, Gaussian) pair of each 16x16 tile
 and its tile list, so that torch autograd differentiates it.  That gives gradients derived independently of
 both the reference's hand-written backward (CR/backward.cu) and the C oracle
-(oracle/gs_oracle.c): `tests/test_gpu_autograd.py` checks the HIP backward
-against them.
+(oracle/gs_oracle.c): `tests/test_autograd_oracle.py` checks the C oracle's and
+the HIP backward against them, `tests/test_blend_replay.py` the fp64 replay
+of the blend.
 
 Semantics follow compat="fixed" (the reference's quirks that only change
 gradients -- Q2 swapped camera arguments, Q3 x_grad_mul, Q5 dead feature

@@ -14,6 +14,16 @@ Tolerances (DESIGN.md section 5 has the measured errors):
   * gradients: relative L2 over all Gaussians <= 1e-4 per output tensor
     (measured <= 2.1e-5, typically ~1e-6), and -- test_gpu_envelope -- within
     10x the oracle's own fp32 summation-order spread in reference mode.
+
+These aggregate bars hold on full-size scenes, where a decision may flip on a
+rare pixel.  tests/test_gpu_elementwise.py adds the per-element guarantee on
+decision-robust scenes (tests/_robust.py; margin factor 8): every pixel and
+every Gaussian within 10 K u A of the fp64 replay of the blend, A its own
+absolute sum.  K_oracle (the fp32 C oracle's own worst) / HIP worst measured:
+colour 21 / 15.1, features 30 / 18.3, depth 18 / 17.5, alpha 3.4 / 3.3,
+dmeans2D 6.2 / 24.6, dopacity 6.6 / 10.1, dcolors 27 / 58.8, dsemantic
+51 / 79.4; behind preprocess_bwd K_down 154, HIP worst 435 (in units of
+u |J| A); same last contributor at every pixel.
 """
 import numpy as np
 import pytest
