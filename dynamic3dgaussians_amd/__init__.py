@@ -15,6 +15,8 @@ Layout:
   resample.py     the reference's bilinear F.interpolate to a prior's size, deterministic (include/gs_resample.h)
   feature_loss.py the reference's feature-distillation loss: resample to the prior, then L1 (+ SSIM)
   densify.py      the reference's clone / split / prune with the Adam state (include/gs_densify.h)
+  scene_loss.py   the reference's floor / bg / soft_col_cons terms and its foreground split, no host syncs
+                  (include/gs_scene_loss.h)
   motion.py       the reference's motion-basis warp: SE(3) basis blend, fused (include/gs_motion.h)
 """
 from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, GradientSink,  # noqa: F401
@@ -27,6 +29,8 @@ from .feature_loss import distillation_image_loss, feature_distillation_loss  # 
 # `densify` here is the function; its module (schedule, plan, classify_torch, ...) is
 # importlib.import_module('dynamic3dgaussians_amd.densify')
 from .densify import densify, densify_torch  # noqa: F401
+from .scene_loss import (foreground_split, gather_foreground, reference_extra_loss, regularizer_losses,  # noqa: F401
+                         regularizer_losses_torch)
 from .motion import (MotionBases, cont_6d_to_rmat, motion_positions, motion_positions_torch,  # noqa: F401
                      motion_transforms)
 

@@ -81,6 +81,14 @@ class GsResample(ctypes.Structure):
                 ("workspace_bytes", ctypes.c_uint64)]
 
 
+class GsSceneLoss(ctypes.Structure):
+    """include/gs_scene_loss.h gs_scene_loss."""
+    _fields_ = [("P", c_int64), ("n_fg", c_int64), ("n_bg", c_int64), ("slot", c_void_p), ("means", c_void_p),
+                ("rotations", c_void_p), ("colors", c_void_p), ("init_bg_pts", c_void_p), ("init_bg_rot", c_void_p),
+                ("prev_col", c_void_p), ("raw_rotations", c_int32), ("_pad", c_int32), ("losses", c_void_p),
+                ("workspace", c_void_p), ("workspace_bytes", ctypes.c_uint64)]
+
+
 GS_DENSIFY_MAX_TENSORS = 16  # include/gs_densify.h
 GS_DENSIFY_N_SPLIT = 2
 GS_DENSIFY_ROLES = {"plain": 0, "means": 1, "log_scales": 2, "rotations": 3, "logit_opacities": 4}
@@ -235,6 +243,18 @@ PROTOTYPES = {
     "gs_resample_axis": (ctypes.c_int, [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "gs_resample_forward": (ctypes.c_int, [ctypes.POINTER(GsResample), c_void_p]),
     "gs_resample_backward": (ctypes.c_int, [ctypes.POINTER(GsResample), c_void_p, c_void_p, c_void_p]),
+    # include/gs_scene_loss.h
+    "gs_scene_loss_struct_bytes": (c_size_t, []),
+    "gs_scene_loss_workspace_bytes": (c_size_t, [c_int64]),
+    "gs_scene_loss_validate": (ctypes.c_int, [ctypes.POINTER(GsSceneLoss), ctypes.c_int, c_void_p, c_void_p, c_void_p,
+                                              c_void_p]),
+    "gs_scene_loss_forward": (ctypes.c_int, [ctypes.POINTER(GsSceneLoss), c_void_p]),
+    "gs_scene_loss_backward": (ctypes.c_int, [ctypes.POINTER(GsSceneLoss), c_void_p, c_void_p, c_void_p, c_void_p,
+                                              c_void_p]),
+    "gs_fg_gather_forward": (ctypes.c_int, [c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_void_p]),
+    "gs_fg_gather_backward": (ctypes.c_int, [c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                             c_void_p]),
     # include/gs_densify.h
     "gs_densify_plan_struct_bytes": (c_size_t, []),
     "gs_densify_tensor_struct_bytes": (c_size_t, []),

@@ -69,6 +69,7 @@ SOURCES = {
     "gs_motion.hip": [],
     "gs_depth_loss.hip": [],
     "gs_resample.hip": [],
+    "gs_scene_loss.hip": ["-ffp-contract=off"],  # act_normalize in the preprocess kernels' order
     "gs_api.hip": [],
     "gs_host.cpp": [],  # host-only C++ (also built by oracle/Makefile's sanitizer target)
     "gs_densify_host.cpp": [],  # host-only C++ (also built into tools/densify_host_sanitize.c's program)
@@ -76,6 +77,7 @@ SOURCES = {
     "gs_motion_host.cpp": [],  # host-only C++ (also built into tools/motion_host_sanitize.c's program)
     "gs_depth_loss_host.cpp": [],  # host-only C++ (also built into tools/depth_loss_host_sanitize.c's program)
     "gs_resample_host.cpp": [],  # host-only C++ (also built into tools/resample_host_sanitize.c's program)
+    "gs_scene_loss_host.cpp": [],  # host-only C++ (also built into tools/scene_loss_host_sanitize.c's program)
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall",
           "-Wno-unused-function", "-I", CSRC, "-I", INCLUDE]

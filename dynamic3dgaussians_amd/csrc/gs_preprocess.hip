@@ -10,6 +10,7 @@
 // computeCov2D, computeCov3D, preprocessCUDA), backward.cu:20-429
 // (computeColorFromSH, computeCov2DCUDA, computeCov3D, preprocessCUDA),
 // auxiliary.h:41-170, rasterizer_impl.cu:54-66 (checkFrustum).
+#include "gs_activate.h"
 #include "gs_common.h"
 #include "gs_kernels.h"
 
@@ -172,29 +173,10 @@ __device__ inline void sh_fwd(int deg, int M, V3 p, V3 cp, const float* __restri
 // without fma contraction): sigmoid = 1 / (1 + exp(-x)), exp, and
 // F.normalize = q / max(|q|, 1e-12) (torch.nn.functional.normalize, p = 2,
 // dim = 1).  Their backward follows autograd's formulas: sigmoid_backward
-// g (1 - y) y, exp's g y, and normalize's div / clamp_min / norm chain.
-// The squared norm is summed pairwise, (x^2 + y^2) + (z^2 + w^2): the order
-// that reproduces torch's GPU reduction bit for bit (tools/act_probe.py on an
-// MI355X: 100 % of 400k quaternions vs 88 % for the sequential sum,
-// profiles/r04b/act_probe.txt).
-constexpr float NORMALIZE_EPS = 1e-12f;
+// g (1 - y) y, exp's g y, and normalize's div / clamp_min / norm chain
+// (act_normalize / act_normalize_bwd, gs_activate.h: shared with the scene
+// regularisers' raw-rotation path).
 __device__ inline float act_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
-__device__ inline float act_norm(float4 q) { return sqrtf((q.x * q.x + q.y * q.y) + (q.z * q.z + q.w * q.w)); }
-__device__ inline float4 act_normalize(float4 q) {
-  const float d = fmaxf(act_norm(q), NORMALIZE_EPS);
-  return make_float4(q.x / d, q.y / d, q.z / d, q.w / d);
-}
-// dL/dq of q_hat = q / max(|q|, eps) for the upstream gradient gq of q_hat:
-// DivBackward (g / d for q, -g (q / d) / d summed for the denominator),
-// ClampMinBackward (passes where |q| >= eps), NormBackward (q (g_n / |q|)).
-__device__ inline float4 act_normalize_bwd(float4 q, float4 gq) {
-  const float n = act_norm(q);
-  const float d = fmaxf(n, NORMALIZE_EPS);
-  const float gd = (-gq.x * ((q.x / d) / d) + -gq.y * ((q.y / d) / d)) +
-                   (-gq.z * ((q.z / d) / d) + -gq.w * ((q.w / d) / d));
-  const float gn = (n >= NORMALIZE_EPS && n != 0.0f) ? gd / n : 0.0f;
-  return make_float4(gq.x / d + q.x * gn, gq.y / d + q.y * gn, gq.z / d + q.z * gn, gq.w / d + q.w * gn);
-}
 // The activated rotation / scale of Gaussian g.
 __device__ inline float4 rotation_of(const float* __restrict__ rotations, int g, int activate) {
   const float4 q = reinterpret_cast<const float4*>(rotations)[g];

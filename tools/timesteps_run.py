@@ -23,7 +23,10 @@ G3 call and fitted with an L1 term (the overlapped feature exchange of the
 sharded step applies); --neighbors: after timestep 0 the foreground k-NN
 graph (initialize_post_first_timestep, train.py:316-341, HIP k-NN) and from
 timestep 1 on the rigidity / rotation / isometry losses (HIP kernels) with
-dyn_train.py's weights 0.4 / 0.4 / 0.2 (dyn_train.py:313); --sharded: the
+dyn_train.py's weights 0.4 / 0.4 / 0.2 (dyn_train.py:313); --regularizers:
+the reference's whole block instead (scene_loss.reference_extra_loss: the
+neighbour terms plus floor / bg / soft_col_cons over a half-foreground seg
+mask, no boolean indexing on the per-step path); --sharded: the
 driver's ShardedStep even at one rank; --per-timestep: every timestep timed
 on its own (device-synchronised) with its peak device memory.
 """
@@ -68,6 +71,8 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--features", type=int, default=0)
     ap.add_argument("--neighbors", action="store_true")
+    ap.add_argument("--regularizers", action="store_true",
+                    help="the reference's whole block (scene_loss.reference_extra_loss) over a half-foreground mask")
     ap.add_argument("--sharded", action="store_true")
     ap.add_argument("--per-timestep", action="store_true")
     ap.add_argument("--out", default="", help="also write the JSON to this file")
@@ -113,7 +118,20 @@ def main():
                                                               generator=gen))
     opt = FusedAdam([{"params": [params[k]], "name": k, "lr": lr} for k, lr in lrs.items()], lr=0.0, eps=1e-15)
     extra, post_first = None, None
-    if a.neighbors:
+    if a.regularizers:
+        from dynamic3dgaussians_amd.scene_loss import reference_extra_loss
+        from dynamic3dgaussians_amd.timesteps import initialize_post_first_timestep
+
+        # seg colours (a constant of the parameterisation, not optimised): every second Gaussian
+        # or so is foreground, so the split, the background anchors and the floor term all work
+        seg = torch.zeros(a.gaussians, 3, device=dev)
+        seg[:, 0] = (torch.rand(a.gaussians, device=dev, generator=gen) < 0.5).float()
+        params["seg_colors"] = seg
+        extra = reference_extra_loss()  # rigid / rot / iso / floor / bg / soft_col_cons, dyn_train.py:313 weights
+
+        def post_first(pr, variables, optimizer):
+            return initialize_post_first_timestep(pr, variables, optimizer, num_knn=20)
+    elif a.neighbors:
         from dynamic3dgaussians_amd.neighbor import neighbor_losses
         from dynamic3dgaussians_amd.timesteps import initialize_post_first_timestep
 
@@ -183,7 +201,7 @@ def main():
             "cams_total": a.cams_total, "cams_per_rank": [len(shard_cameras(a.cams_total, r, world))
                                                           for r in range(world)],
             "gaussians": a.gaussians, "size": [W, H], "mean_loss_per_timestep": [round(x, 6) for x in loss_per_t],
-            "features": a.features, "neighbors": a.neighbors,
+            "features": a.features, "neighbors": a.neighbors, "regularizers": a.regularizers,
             "optimizer_step": ("distributed.ShardedStep" + (" (features overlapped)" if drv.zs.overlap else "")
                                if drv.zs is not None else "GradBucket all-reduce + FusedAdam"),
             "data": "synthetic (targets: the rig's renders of the scene before a colour jitter)"}
