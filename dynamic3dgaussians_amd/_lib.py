@@ -89,6 +89,13 @@ class GsSceneLoss(ctypes.Structure):
                 ("workspace", c_void_p), ("workspace_bytes", ctypes.c_uint64)]
 
 
+class GsImageMetrics(ctypes.Structure):
+    """include/gs_metrics.h struct gs_image_metrics."""
+    _fields_ = [("B", c_int32), ("Ch", c_int32), ("H", c_int32), ("W", c_int32), ("pred", c_void_p),
+                ("target", c_void_p), ("mask", c_void_p), ("mask_batch_stride", c_int64), ("want_ssim", c_int32),
+                ("_pad", c_int32), ("out", c_void_p), ("workspace", c_void_p), ("workspace_bytes", ctypes.c_uint64)]
+
+
 GS_DENSIFY_MAX_TENSORS = 16  # include/gs_densify.h
 GS_DENSIFY_N_SPLIT = 2
 GS_DENSIFY_ROLES = {"plain": 0, "means": 1, "log_scales": 2, "rotations": 3, "logit_opacities": 4}
@@ -255,6 +262,13 @@ PROTOTYPES = {
                                             c_void_p]),
     "gs_fg_gather_backward": (ctypes.c_int, [c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                              c_void_p]),
+    # include/gs_metrics.h
+    "gs_image_metrics_struct_bytes": (c_size_t, []),
+    "gs_image_metrics_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
+    "gs_image_metrics_validate": (ctypes.c_int, [ctypes.POINTER(GsImageMetrics)]),
+    "gs_image_metrics": (ctypes.c_int, [ctypes.POINTER(GsImageMetrics), c_void_p]),
+    "gs_mask_iou_validate": (ctypes.c_int, [c_int32, c_int64, c_void_p, c_void_p, c_float, c_void_p]),
+    "gs_mask_iou": (ctypes.c_int, [c_int32, c_int64, c_void_p, c_void_p, c_float, c_void_p, c_void_p]),
     # include/gs_densify.h
     "gs_densify_plan_struct_bytes": (c_size_t, []),
     "gs_densify_tensor_struct_bytes": (c_size_t, []),
