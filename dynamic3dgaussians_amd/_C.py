@@ -107,10 +107,13 @@ def _compat_code(compat) -> int:
     return _lib.GS_COMPAT[mode]
 
 
-def _num_points(means3D) -> int:
+def _num_points(means3D, windowed=False) -> int:
     """P of a call, after the two checks every call answers before anything
-    else is looked at."""
-    if means3D.ndimension() != 2 or means3D.size(1) != 3:
+    else is looked at.  `windowed`: a temporal window's (P, B, 3) means."""
+    if windowed:
+        if means3D.ndimension() != 3 or means3D.size(2) != 3:
+            raise RuntimeError("means3D must have dimensions (num_points, frames, 3) with cam_frames")
+    elif means3D.ndimension() != 2 or means3D.size(1) != 3:
         raise RuntimeError("means3D must have dimensions (num_points, 3)")  # rasterize_points.cu:60-62
     if means3D.device.type != "cuda":
         raise _lib.GsplatError("the HIP rasterizer needs device tensors (means3D is on the CPU)")
@@ -271,6 +274,12 @@ def _event_handle(ev) -> int:
     return 0 if ev is None else int(ev.cuda_event)
 
 
+def _frames_arg(cam_frames):
+    """A temporal window's per-camera frames as the native binding takes
+    them: C ints, or an empty list for none."""
+    return [] if cam_frames is None else [int(f) for f in cam_frames]
+
+
 def _windows_arg(windows):
     """Tile windows as the native binding takes them: C x [x0, y0, x1, y1]
     (all 0 = the whole image), or an empty list for none."""
@@ -332,7 +341,7 @@ def rasterize_gaussians_batch(background, means3D, colors, semantic_feature, opa
                               scale_modifier, cov3D_precomp, viewmatrices, projmatrices, c_x, c_y, tan_fovx,
                               tan_fovy, image_height, image_width, sh, degree, campos, prefiltered, debug,
                               *, compat=None, activate=False, windows=None, feature_ready=None, plan_state=None,
-                              walk_order=None, zero_fill=None):
+                              walk_order=None, zero_fill=None, cam_frames=None):
     """The forward of C cameras at once (gs_forward_plan_batch +
     gs_forward_render_batch): the arguments of rasterize_gaussians with
     per-camera matrices stacked ([C,4,4] or [C,16], campos [C,3]) and the
@@ -356,10 +365,13 @@ def rasterize_gaussians_batch(background, means3D, colors, semantic_feature, opa
     (gs_gaussians.walk_order; outputs do not depend on it).  `zero_fill`: a
     device tensor the blend zeroes (its whole bytes, rounded down to 16) --
     the backward's scratch, handed to rasterize_gaussians_batch_backward
-    with scratch_zeroed=True (gs_gaussians.zero_fill, ABI 13)."""
+    with scratch_zeroed=True (gs_gaussians.zero_fill, ABI 13).  `cam_frames`:
+    a temporal window (include/gs_window.h) -- C non-decreasing frame indices;
+    means3D is then (P, B, 3) Gaussian-major and camera c renders
+    means3D[:, cam_frames[c]]; everything else is shared by the frames."""
     sync_free = plan_state is not None and not debug
     cm = _compat_code(compat)
-    P, C = _num_points(means3D), len(c_x)
+    P, C = _num_points(means3D, cam_frames is not None), len(c_x)
     if P == 0:  # answered before any camera argument is looked at
         H, W = int(image_height), int(image_width)
         f32 = dict(dtype=torch.float32, device=means3D.device)
@@ -384,7 +396,7 @@ def rasterize_gaussians_batch(background, means3D, colors, semantic_feature, opa
             [float(x) for x in c_y], [float(x) for x in tan_fovx], [float(x) for x in tan_fovy], int(image_height),
             int(image_width), _opt(sh), int(degree), campos, bool(prefiltered), bool(debug), cm, bool(activate),
             _windows_arg(windows), _event_handle(feature_ready), cap, plan_state.hint if sync_free else [],
-            _opt(walk_order), _opt(zero_fill), _lib.stream(means3D.device))
+            _opt(walk_order), _opt(zero_fill), _frames_arg(cam_frames), _lib.stream(means3D.device))
     except RuntimeError as ex:
         raise _lib.GsplatError(str(ex)) from None
     NR, color, fmap, depth, alpha, radii, geom, binning, img, NI, layout, hint, fitted = out
@@ -401,7 +413,7 @@ def rasterize_gaussians_batch_backward(background, means3D, radii, colors, seman
                                        num_instances, binningBuffer, imageBuffer, alphas, debug, *,
                                        compat=None, grad_mask=None, densify=None, opacity=None,
                                        activate=False, windows=None, out=None, scratch=None,
-                                       scratch_zeroed=False):
+                                       scratch_zeroed=False, cam_frames=None):
     """The backward of a camera batch (gs_backward_batch): the arguments of
     rasterize_gaussians_backward with stacked per-camera matrices, scalars
     and upstream gradients ([C, ...]), in the binding's positional camera
@@ -417,13 +429,16 @@ def rasterize_gaussians_batch_backward(background, means3D, radii, colors, seman
     element count (dsem at the compiled feature width).  `scratch`: the
     backward's scratch (gs_batch_backward_scratch_bytes) kept from the
     forward, `scratch_zeroed`: the forward's blend zeroed it
-    (rasterize_gaussians_batch zero_fill; GS_FLAG_SCRATCH_ZEROED)."""
+    (rasterize_gaussians_batch zero_fill; GS_FLAG_SCRATCH_ZEROED).
+    `cam_frames`: the forward's temporal window; means3D is (P, B, 3) and so is
+    dL_dmeans3D (and its `out` destination): frame b holds the sum over the
+    cameras of frame b, zeros for a frame without cameras."""
     return _backward(background, means3D, radii, colors, semantic_feature, scales, rotations, scale_modifier,
                      cov3D_precomp, viewmatrices, projmatrices, c_x, c_y, tan_fovx, tan_fovy, dL_dout_color,
                      dL_dout_feature, dL_dout_depth, dL_dout_alpha, sh, degree, campos, geomBuffer, num_instances,
                      binningBuffer, imageBuffer, alphas, debug, compat=compat, grad_mask=grad_mask, densify=densify,
                      opacity=opacity, activate=activate, windows=windows, out=out, scratch=scratch,
-                     scratch_zeroed=scratch_zeroed)
+                     scratch_zeroed=scratch_zeroed, cam_frames=cam_frames)
 
 
 def _backward(background, means3D, radii, colors, semantic_feature, scales, rotations, scale_modifier,
@@ -431,7 +446,7 @@ def _backward(background, means3D, radii, colors, semantic_feature, scales, rota
               dL_dout_feature, dL_dout_depth, dL_dout_alpha, sh, degree, campos, geomBuffer, num_instances,
               binningBuffer, imageBuffer, alphas, debug, *, compat, grad_mask, densify, opacity=None,
               activate=False, windows=None, out=None, exact_out=False, accumulate=False, scratch=None,
-              scratch_zeroed=False):
+              scratch_zeroed=False, cam_frames=None):
     """The one backward body, for C = len(c_x) cameras (gs_backward_batch; at
     C = 1 what the single-camera entry point runs).  `exact_out`: `out` holds every gradient
     name in its exact shape (else any subset, by element count);
@@ -445,9 +460,11 @@ def _backward(background, means3D, radii, colors, semantic_feature, scales, rota
         odd = _BUFFER_NAMES - out.keys() if exact_out else out.keys() - _BUFFER_NAMES
         if odd:
             raise RuntimeError(f"out: {'missing' if exact_out else 'unknown'} gradient names {sorted(odd)}")
-    if _num_points(means3D) == 0:  # answered before any camera argument is looked at
-        return tuple(torch.zeros(*shape, dtype=torch.float32, device=means3D.device)
-                     for shape in _buffer_shapes(0, 0, 0).values())
+    if _num_points(means3D, cam_frames is not None) == 0:  # answered before any camera argument is looked at
+        shapes = _buffer_shapes(0, 0, 0)
+        if cam_frames is not None:
+            shapes["dmeans3D"] = (0, means3D.size(1), 3)
+        return tuple(torch.zeros(*shape, dtype=torch.float32, device=means3D.device) for shape in shapes.values())
     try:
         return tuple(_native_mod().backward_batch(
             background, means3D, radii, _opt(colors), _opt(semantic_feature), _opt(scales), _opt(rotations),
@@ -458,6 +475,6 @@ def _backward(background, means3D, radii, colors, semantic_feature, scales, rota
             alphas, bool(debug), cm, _opt(grad_mask), None if densify is None else list(densify),
             _opt(opacity), bool(activate), _windows_arg(windows),
             [out.get(k, _NO_DEST) for k in _BUFFER_ORDER] if out else [], bool(exact_out), bool(accumulate),
-            _opt(scratch), bool(scratch_zeroed), _lib.stream(means3D.device)))
+            _opt(scratch), bool(scratch_zeroed), _frames_arg(cam_frames), _lib.stream(means3D.device)))
     except RuntimeError as ex:
         raise _lib.GsplatError(str(ex)) from None

@@ -162,7 +162,17 @@ class GsBatchHint(ctypes.Structure):
                 ("max_len", c_int64), ("total", c_int64)]
 
 
+GS_WINDOW_MAX_FRAMES = 64  # include/gs_window.h
+
+
+class GsWindow(ctypes.Structure):
+    """include/gs_window.h gs_window: a temporal window of B frames of means3D
+    (P x B x 3) and each camera's frame (host array, non-decreasing)."""
+    _fields_ = [("B", c_int32), ("cam_frame", ctypes.POINTER(c_int32))]
+
+
 P_G = ctypes.POINTER(GsGaussians)
+P_W = ctypes.POINTER(GsWindow)
 P_NG = ctypes.POINTER(GsNeighborGraph)
 P_C = ctypes.POINTER(GsCamera)
 
@@ -202,6 +212,21 @@ PROTOTYPES = {
                                          c_void_p, c_void_p, ctypes.POINTER(c_int64), c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # include/gs_window.h: the batch calls with a window before the stream
+    "gs_check_window": (ctypes.c_int, [P_W, c_int32]),
+    "gs_forward_plan_batch_window": (ctypes.c_int, [P_G, P_C, c_int32, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                    c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_int64),
+                                                    ctypes.POINTER(c_int64), P_W, c_void_p]),
+    "gs_forward_batch_window": (ctypes.c_int, [P_G, P_C, c_int32, ctypes.c_int, ctypes.c_int, c_void_p, c_void_p,
+                                               c_void_p, ctypes.POINTER(c_int64), ctypes.POINTER(GsBatchHint),
+                                               c_void_p, ctypes.POINTER(c_int64), ctypes.POINTER(c_int64),
+                                               ctypes.POINTER(c_int32), c_void_p, c_void_p, c_void_p, c_void_p, P_W,
+                                               c_void_p]),
+    "gs_backward_batch_window": (ctypes.c_int, [P_G, P_C, c_int32, c_void_p, ctypes.c_int, ctypes.c_int, c_void_p,
+                                                c_void_p, c_void_p, ctypes.POINTER(c_int64), c_void_p, c_void_p,
+                                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                c_void_p, P_W, c_void_p]),
     "gs_mark_visible": (ctypes.c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gs_debug_export": (ctypes.c_int, [c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
                                        c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -80,6 +80,7 @@ SOURCES = {
     "gs_resample_host.cpp": [],  # host-only C++ (also built into tools/resample_host_sanitize.c's program)
     "gs_scene_loss_host.cpp": [],  # host-only C++ (also built into tools/scene_loss_host_sanitize.c's program)
     "gs_metrics_host.cpp": [],  # host-only C++ (also built into tools/metrics_host_sanitize.c's program)
+    "gs_window_host.cpp": [],  # host-only C++ (also built into tools/window_host_sanitize.c's program)
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall",
           "-Wno-unused-function", "-I", CSRC, "-I", INCLUDE]

@@ -16,6 +16,7 @@
 #include <thread>
 #include <vector>
 
+#include "../../include/gs_window.h"
 #include "../../include/gsplat_hip.h"
 #include "gs_common.h"
 #include "gs_kernels.h"
@@ -293,10 +294,20 @@ size_t gs_backward_scratch_bytes(int64_t P, int32_t F) { return gs_batch_backwar
 
 // The batch's CamBatch from C gs_camera blocks: matrices contiguous per
 // camera (camera c's at camera 0's + 16 c / + 3 c), one shared background.
-static int make_batch(const gs_camera* cams, int C, int P, int W, int H, CamBatch& cb) {
+// win: the temporal window of the calls that read the means (gs_window.h), or
+// null (B = 1, every camera at frame 0).
+static_assert(GS_WINDOW_MAX_FRAMES == GS_MAX_FRAMES && GS_MAX_FRAMES <= 256, "gs_window.h and CamBatch::frame");
+static int make_batch(const gs_camera* cams, int C, int P, int W, int H, CamBatch& cb,
+                      const gs_window* win = nullptr) {
   if (C < 1 || C > GS_MAX_CAMS) return fail(-1, "camera batch size %d outside 1..%d", C, GS_MAX_CAMS);
   cb = CamBatch{};
   cb.C = C;
+  cb.B = 1;
+  if (win) {
+    if (int e = gs_check_window(win, C)) return e;
+    cb.B = win->B;
+    for (int c = 0; c < C; ++c) cb.frame[c] = (uint8_t)win->cam_frame[c];
+  }
   cb.geom_stride = (int64_t)GeomLayout(P).total;
   cb.img_stride = (int64_t)ImgLayout(W, H).total;
   cb.view = cams[0].viewmatrix;
@@ -381,10 +392,11 @@ static int debug_check_lists(const TileArgs& ta, const CamBatch& cb, const void*
 // The plan's kernels (preprocess, tile histogram, column scan, offsets), the
 // headers published to hdr_dev (mapped host memory) by the last of them.
 static int plan_enqueue(const gs_gaussians* g, const gs_camera* cams, int C, int prefiltered, int debug, void* geom,
-                        void* image, int32_t* radii, uint32_t* hdr_dev, CamBatch& cb, hipStream_t s) {
+                        void* image, int32_t* radii, uint32_t* hdr_dev, CamBatch& cb, const gs_window* win,
+                        hipStream_t s) {
   const int P = g->P;
   const int W = cams[0].image_width, H = cams[0].image_height;
-  if (int e = make_batch(cams, C, P, W, H, cb)) return e;
+  if (int e = make_batch(cams, C, P, W, H, cb, win)) return e;
   const GeomLayout gl(P);
   if (debug && g->walk_order && P > 0) {
     // debug mode: the walk order must be a permutation of the ids (a
@@ -495,7 +507,7 @@ static void header_sentinel(HeaderLease& hl, int C) {
 
 static int plan_impl(const gs_gaussians* g, const gs_camera* cams, int C, int prefiltered, int debug, int compat,
                      void* geom, void* image, int32_t* radii, int64_t* num_rendered, int64_t* num_instances,
-                     hipStream_t s) {
+                     const gs_window* win, hipStream_t s) {
   if (int e = check_gaussians(g, cams, true)) return e;
   if (!num_rendered) return fail(-1, "num_rendered is null");
   for (int c = 0; c < C; ++c) {
@@ -511,7 +523,7 @@ static int plan_impl(const gs_gaussians* g, const gs_camera* cams, int C, int pr
   header_sentinel(hl, C);
   CamBatch cb;
   hl.launched(s);
-  if (int e = plan_enqueue(g, cams, C, prefiltered, debug, geom, image, radii, hl.s.dev, cb, s))
+  if (int e = plan_enqueue(g, cams, C, prefiltered, debug, geom, image, radii, hl.s.dev, cb, win, s))
     return e;
   // The one host read of the forward (CR/rasterizer_impl.cu:287), one for
   // the whole batch: the list instance counts size the binning buffer; the
@@ -618,7 +630,8 @@ static int backward_impl(const gs_gaussians* g, const gs_camera* cams, int C, co
                          const float* alphas, const float* dL_dout_color, const float* dL_dout_feature,
                          const float* dL_dout_depth, const float* dL_dout_alpha, void* scratch, float* dL_dmeans2D,
                          float* dL_dcolors, float* dL_dsemantic, float* dL_dopacity, float* dL_dmeans3D,
-                         float* dL_dcov3D, float* dL_dsh, float* dL_dscales, float* dL_drotations, hipStream_t s) {
+                         float* dL_dcov3D, float* dL_dsh, float* dL_dscales, float* dL_drotations,
+                         const gs_window* win, hipStream_t s) {
   if (int e = check_gaussians(g, cams, false)) return e;
   const int P = g->P;
   if (P == 0) return 0;
@@ -631,7 +644,7 @@ static int backward_impl(const gs_gaussians* g, const gs_camera* cams, int C, co
     return fail(-1, "gradient outputs are required");
   const int W = cams[0].image_width, H = cams[0].image_height;
   CamBatch cb;
-  if (int e = make_batch(cams, C, P, W, H, cb)) return e;
+  if (int e = make_batch(cams, C, P, W, H, cb, win)) return e;
   // the tile lists sit at the start of each camera's binning buffer and the
   // ranges say how long they are (an empty binning buffer: every list empty)
   batch_bin_offsets(C, L, &cb);
@@ -716,7 +729,7 @@ int gs_forward_plan(const gs_gaussians* g, const gs_camera* cam, int prefiltered
                     gs_stream_t stream) {
   if (!cam) return fail(-1, "null argument block");
   return plan_impl(g, cam, 1, prefiltered, debug, compat, geom, image, radii, num_rendered, num_instances,
-                   (hipStream_t)stream);
+                   nullptr, (hipStream_t)stream);
 }
 
 int gs_forward_render(const gs_gaussians* g, const gs_camera* cam, int debug, int compat, void* geom,
@@ -740,7 +753,7 @@ int gs_backward(const gs_gaussians* g, const gs_camera* cam, const int32_t* radi
   return backward_impl(g, cam, 1, radii, debug, compat, geom, binning, image, &L0, alphas, dL_dout_color,
                        dL_dout_feature, dL_dout_depth, dL_dout_alpha, scratch, dL_dmeans2D, dL_dcolors,
                        dL_dsemantic, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales, dL_drotations,
-                       (hipStream_t)stream);
+                       nullptr, (hipStream_t)stream);
 }
 
 size_t gs_batch_geom_buffer_bytes(int64_t P, int32_t C) { return GeomLayout(P > 0 ? P : 0).total * (C > 0 ? C : 0); }
@@ -753,13 +766,25 @@ size_t gs_batch_backward_scratch_bytes(int64_t P, int32_t F, int32_t C) {
   return acc_bytes(P, C) + feat_pad_bytes(P, F) + 256;
 }
 
+// ---- temporal windows (include/gs_window.h): the batch entry points that
+// read the means take a window; without one (win = null) they are the calls
+// below them.
+int gs_forward_plan_batch_window(const gs_gaussians* g, const gs_camera* cams, int32_t C, int prefiltered, int debug,
+                                 int compat, void* geom, void* image, int32_t* radii, int64_t* num_rendered,
+                                 int64_t* num_instances, const gs_window* win, gs_stream_t stream) {
+  if (!cams) return fail(-1, "null argument block");
+  if (C < 1 || C > GS_MAX_CAMS) return fail(-1, "camera batch size %d outside 1..%d", C, GS_MAX_CAMS);
+  if (win)
+    if (int e = gs_check_window(win, C)) return e;
+  return plan_impl(g, cams, C, prefiltered, debug, compat, geom, image, radii, num_rendered, num_instances, win,
+                   (hipStream_t)stream);
+}
+
 int gs_forward_plan_batch(const gs_gaussians* g, const gs_camera* cams, int32_t C, int prefiltered, int debug,
                           int compat, void* geom, void* image, int32_t* radii, int64_t* num_rendered,
                           int64_t* num_instances, gs_stream_t stream) {
-  if (!cams) return fail(-1, "null argument block");
-  if (C < 1 || C > GS_MAX_CAMS) return fail(-1, "camera batch size %d outside 1..%d", C, GS_MAX_CAMS);
-  return plan_impl(g, cams, C, prefiltered, debug, compat, geom, image, radii, num_rendered, num_instances,
-                   (hipStream_t)stream);
+  return gs_forward_plan_batch_window(g, cams, C, prefiltered, debug, compat, geom, image, radii, num_rendered,
+                                      num_instances, nullptr, stream);
 }
 
 int gs_forward_render_batch(const gs_gaussians* g, const gs_camera* cams, int32_t C, int debug, int compat,
@@ -811,8 +836,20 @@ int gs_forward_batch(const gs_gaussians* g, const gs_camera* cams, int32_t C, in
                      void* geom, void* image, void* binning, const int64_t* capacity, gs_batch_hint* hint,
                      int32_t* radii, int64_t* num_rendered, int64_t* num_instances, int32_t* fits,
                      float* out_color, float* out_feature, float* out_depth, float* out_alpha, gs_stream_t stream) {
+  return gs_forward_batch_window(g, cams, C, prefiltered, compat, geom, image, binning, capacity, hint, radii,
+                                 num_rendered, num_instances, fits, out_color, out_feature, out_depth, out_alpha,
+                                 nullptr, stream);
+}
+
+int gs_forward_batch_window(const gs_gaussians* g, const gs_camera* cams, int32_t C, int prefiltered, int compat,
+                            void* geom, void* image, void* binning, const int64_t* capacity, gs_batch_hint* hint,
+                            int32_t* radii, int64_t* num_rendered, int64_t* num_instances, int32_t* fits,
+                            float* out_color, float* out_feature, float* out_depth, float* out_alpha,
+                            const gs_window* win, gs_stream_t stream) {
   if (!cams || !capacity || !num_rendered || !num_instances || !fits) return fail(-1, "null argument block");
   if (C < 1 || C > GS_MAX_CAMS) return fail(-1, "camera batch size %d outside 1..%d", C, GS_MAX_CAMS);
+  if (win)
+    if (int e = gs_check_window(win, C)) return e;
   if (int e = check_gaussians(g, cams, true)) return e;
   *fits = 1;
   for (int c = 0; c < C; ++c) {
@@ -835,7 +872,7 @@ int gs_forward_batch(const gs_gaussians* g, const gs_camera* cams, int32_t C, in
   hipStream_t s = (hipStream_t)stream;
   CamBatch cb;
   hl.launched(s);
-  if (int e = plan_enqueue(g, cams, C, prefiltered, 0, geom, image, radii, hl.s.dev, cb, s))
+  if (int e = plan_enqueue(g, cams, C, prefiltered, 0, geom, image, radii, hl.s.dev, cb, win, s))
     return e;
   const int W = cams[0].image_width, H = cams[0].image_height;
   const TileArgs ta = tile_args(P, W, H, geom, image);
@@ -869,6 +906,23 @@ int gs_forward_batch(const gs_gaussians* g, const gs_camera* cams, int32_t C, in
   return 0;
 }
 
+int gs_backward_batch_window(const gs_gaussians* g, const gs_camera* cams, int32_t C, const int32_t* radii, int debug,
+                             int compat, const void* geom, const void* binning, const void* image,
+                             const int64_t* num_instances, const float* alphas, const float* dL_dout_color,
+                             const float* dL_dout_feature, const float* dL_dout_depth, const float* dL_dout_alpha,
+                             void* scratch, float* dL_dmeans2D, float* dL_dcolors, float* dL_dsemantic,
+                             float* dL_dopacity, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh,
+                             float* dL_dscales, float* dL_drotations, const gs_window* win, gs_stream_t stream) {
+  if (!cams || !num_instances) return fail(-1, "null argument block");
+  if (C < 1 || C > GS_MAX_CAMS) return fail(-1, "camera batch size %d outside 1..%d", C, GS_MAX_CAMS);
+  if (win)
+    if (int e = gs_check_window(win, C)) return e;
+  return backward_impl(g, cams, C, radii, debug, compat, geom, binning, image, num_instances, alphas,
+                       dL_dout_color, dL_dout_feature, dL_dout_depth, dL_dout_alpha, scratch, dL_dmeans2D,
+                       dL_dcolors, dL_dsemantic, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales,
+                       dL_drotations, win, (hipStream_t)stream);
+}
+
 int gs_backward_batch(const gs_gaussians* g, const gs_camera* cams, int32_t C, const int32_t* radii, int debug,
                       int compat, const void* geom, const void* binning, const void* image,
                       const int64_t* num_instances, const float* alphas, const float* dL_dout_color,
@@ -876,12 +930,10 @@ int gs_backward_batch(const gs_gaussians* g, const gs_camera* cams, int32_t C, c
                       void* scratch, float* dL_dmeans2D, float* dL_dcolors, float* dL_dsemantic,
                       float* dL_dopacity, float* dL_dmeans3D, float* dL_dcov3D, float* dL_dsh, float* dL_dscales,
                       float* dL_drotations, gs_stream_t stream) {
-  if (!cams || !num_instances) return fail(-1, "null argument block");
-  if (C < 1 || C > GS_MAX_CAMS) return fail(-1, "camera batch size %d outside 1..%d", C, GS_MAX_CAMS);
-  return backward_impl(g, cams, C, radii, debug, compat, geom, binning, image, num_instances, alphas,
-                       dL_dout_color, dL_dout_feature, dL_dout_depth, dL_dout_alpha, scratch, dL_dmeans2D,
-                       dL_dcolors, dL_dsemantic, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales,
-                       dL_drotations, (hipStream_t)stream);
+  return gs_backward_batch_window(g, cams, C, radii, debug, compat, geom, binning, image, num_instances, alphas,
+                                  dL_dout_color, dL_dout_feature, dL_dout_depth, dL_dout_alpha, scratch,
+                                  dL_dmeans2D, dL_dcolors, dL_dsemantic, dL_dopacity, dL_dmeans3D, dL_dcov3D,
+                                  dL_dsh, dL_dscales, dL_drotations, nullptr, stream);
 }
 
 int gs_mark_visible(int64_t P, const float* means3D, const float* viewmatrix, const float* projmatrix,

@@ -168,7 +168,14 @@ struct ImgLayout {
 // images and radii [C, ...].  Kernels take the camera from blockIdx.y (or
 // the minor index of a flattened grid); the single-camera entry points are
 // the C = 1 case.  Camera parameters ride in the kernel arguments.
+//
+// Temporal windows (include/gs_window.h): means3D holds B frames per Gaussian,
+// Gaussian-major (frame b of Gaussian g at 3 (g B + b)), and camera c reads
+// frame `frame[c]`; the frames are non-decreasing in c.  Only the two
+// preprocess kernels read the means, so nothing else looks at B or frame.
+// Without a window B = 1 and every frame is 0.
 constexpr int GS_MAX_CAMS = 64;
+constexpr int GS_MAX_FRAMES = 64;
 struct CamBatch {
   int C;
   int64_t geom_stride;   // bytes between the cameras' geometry buffers
@@ -180,7 +187,16 @@ struct CamBatch {
   int64_t bin_off[GS_MAX_CAMS];  // byte offset of camera c's binning buffer
   int64_t bin_L[GS_MAX_CAMS];    // camera c's tile-list length (instances)
   uint16_t win[GS_MAX_CAMS][4];  // camera c's tile window [x0, x1) x [y0, y1) (gs_camera tile_*)
+  uint8_t frame[GS_MAX_CAMS];    // camera c's frame of means3D, non-decreasing in c (all 0 without a window)
+  int B;                         // frames per Gaussian in means3D (1 without a window)
 };
+// kernel arguments are limited to 4 KB: the camera table plus the largest
+// argument block next to it (PreprocessBwdArgs, < 512 B) must stay under it
+static_assert(sizeof(CamBatch) <= 4096 - 512, "CamBatch outgrew the kernel-argument budget");
+// the mean of Gaussian g as camera c of the batch sees it
+__host__ __device__ inline size_t mean_offset(const CamBatch& cb, int c, int g) {
+  return 3 * ((size_t)g * cb.B + cb.frame[c]);
+}
 __host__ __device__ inline bool in_window(const CamBatch& cb, int c, int tx, int ty) {
   return tx >= cb.win[c][0] && tx < cb.win[c][2] && ty >= cb.win[c][1] && ty < cb.win[c][3];
 }

@@ -227,8 +227,8 @@ __global__ __launch_bounds__(256) void preprocess_fwd_kernel(PreprocessArgs a0, 
     a.tiles[g] = 0;
     a.rect[g] = make_uint4(0u, 0u, 0u, 0u);
   };
-  const V3 p = ld3(a.means3D + 3 * g);
-  // The 3D covariance does not depend on the camera: the batch's camera 0
+  const V3 p = ld3(a.means3D + mean_offset(batch, cam, g));  // the mean at this camera's frame
+  // The 3D covariance does not depend on the camera or its frame: the batch's camera 0
   // stores it for every Gaussian (before the frustum test, so a Gaussian
   // camera 0 does not see still has it) and preprocess_bwd reads it there
   // once per Gaussian; the other cameras compute it without storing.
@@ -450,24 +450,43 @@ __device__ inline void cov3d_bwd(V3 scale, float mod, float4 rot, const float d[
 // order and sums their contributions in registers (deterministic, one write
 // per output), so a batch costs one pass over the Gaussian state instead of
 // C read-modify-write passes.  Every output element is written, so outputs
-// need no zero-fill.
+// need no zero-fill.  dL/dmeans3D is P x B x 3: frame b receives the sum over
+// the cameras of frame b (zeros when it has none).
 constexpr int PB_GROUP = 2;  // cameras whose operands are requested together
 // SH: the SH-coefficient backward is compiled in (launched when a.shs is set);
 // the precomputed-colour instantiation carries none of its registers.
-template <bool SH>
+// WIN: a temporal window (B > 1 frames of means, include/gs_window.h).
+template <bool SH, bool WIN>
 __global__ __launch_bounds__(256) void preprocess_bwd_kernel(PreprocessBwdArgs a, CamBatch cb) {
   const int g = blockIdx.x * 256 + threadIdx.x;
   if (g >= a.P) return;
   const int ac = a.accumulate;
   const bool masked = a.grad_mask != nullptr;
   const float mk = masked ? a.grad_mask[g] : 1.f;
-  const V3 mean = ld3(a.means3D + 3 * g);
+  // The mean and its gradient belong to the camera's frame (CamBatch::frame,
+  // non-decreasing): the walk below keeps one frame's mean and mean-gradient
+  // sum in registers and, when the frame changes, stores the sum (put_mean),
+  // writes zeros for the frames no camera uses and loads the next frame's
+  // mean.  Everything else is summed over all cameras of all frames.  Without
+  // a window (WIN = false: B = 1, every frame 0) the frame never changes and
+  // the frame handling folds away.
+  const int B = WIN ? cb.B : 1;
+  auto frame_of = [&](int c) { return WIN ? (int)cb.frame[c] : 0; };
+  int fcur = frame_of(0);
+  V3 mean = ld3(a.means3D + 3 * ((size_t)g * B + fcur));
+  auto put_mean = [&](int f, float x, float y, float z) {
+    float* d = a.dmeans3D + 3 * ((size_t)g * B + f);
+    gput(d, x * mk, ac); gput(d + 1, y * mk, ac); gput(d + 2, z * mk, ac);
+  };
+  for (int f = 0; f < fcur; ++f) put_mean(f, 0.f, 0.f, 0.f);
   // camera sums (the first camera assigns, so C = 1 is the single-view value)
   float am[2] = {0.f, 0.f}, dcol[3] = {0.f, 0.f, 0.f}, dop = 0.f;
-  float dm[3] = {0.f, 0.f, 0.f};
+  float dm[3] = {0.f, 0.f, 0.f};  // of the frame fcur
   float dcov[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   float st_acc = 0.f, st_den = 0.f, st_rad = 0.f;
-  bool any_vis = false, sh_written = ac != 0;
+  // any_vis: some camera saw the Gaussian (scale / rotation path); mean_vis:
+  // some camera of the frame fcur did (the first of them assigns dm)
+  bool any_vis = false, mean_vis = false, sh_written = ac != 0;
   // The cameras are walked in groups of PB_GROUP: every operand of a group
   // (radius, accumulation record, conic, 3D covariance of each camera) is
   // requested before the first of them is used, so the group's loads are in
@@ -500,6 +519,14 @@ __global__ __launch_bounds__(256) void preprocess_bwd_kernel(PreprocessBwdArgs a
   for (int k = 0; k < PB_GROUP; ++k) {
     const int c = cg + k;
     if (c >= cb.C) break;
+    if (WIN && frame_of(c) != fcur) {  // wave-uniform: the next frame starts with this camera
+      put_mean(fcur, dm[0], dm[1], dm[2]);
+      for (int f = fcur + 1; f < frame_of(c); ++f) put_mean(f, 0.f, 0.f, 0.f);
+      fcur = frame_of(c);
+      mean = ld3(a.means3D + 3 * ((size_t)g * B + fcur));
+      dm[0] = 0.f; dm[1] = 0.f; dm[2] = 0.f;
+      mean_vis = false;
+    }
     const bool first = c == 0;
     auto add = [&](float& sum, float v) { sum = first ? v : sum + v; };
     const float* acc = acck[k];
@@ -612,11 +639,13 @@ __global__ __launch_bounds__(256) void preprocess_bwd_kernel(PreprocessBwdArgs a
       sh_written = true;
     }
     // the first camera that sees the Gaussian assigns, the later ones add
+    // (the mean gradient: the first camera of the frame)
 #pragma unroll
-    for (int i = 0; i < 3; ++i) dm[i] = any_vis ? dm[i] + dmc[i] : dmc[i];
+    for (int i = 0; i < 3; ++i) dm[i] = mean_vis ? dm[i] + dmc[i] : dmc[i];
 #pragma unroll
     for (int i = 0; i < 6; ++i) dcov[i] = any_vis ? dcov[i] + dcv[i] : dcv[i];
     any_vis = true;
+    mean_vis = true;
   }
   }
   float dscale[3] = {0.f, 0.f, 0.f}, drot[4] = {0.f, 0.f, 0.f, 0.f};
@@ -647,8 +676,8 @@ __global__ __launch_bounds__(256) void preprocess_bwd_kernel(PreprocessBwdArgs a
     float* ds = a.dsh + (size_t)g * a.M * 3;
     for (int i = 0; i < 3 * a.M; ++i) ds[i] = 0.f * mk;
   }
-#pragma unroll
-  for (int i = 0; i < 3; ++i) gput(a.dmeans3D + 3 * g + i, dm[i] * mk, ac);
+  put_mean(fcur, dm[0], dm[1], dm[2]);
+  for (int f = fcur + 1; f < B; ++f) put_mean(f, 0.f, 0.f, 0.f);
 #pragma unroll
   for (int i = 0; i < 6; ++i) gput(a.dcov3D + 6 * g + i, dcov[i] * mk, ac);
   if (act && a.scales) {
@@ -675,10 +704,12 @@ __global__ __launch_bounds__(256) void preprocess_bwd_kernel(PreprocessBwdArgs a
 
 void launch_preprocess_bwd(const PreprocessBwdArgs& a, const CamBatch& cb, hipStream_t s) {
   if (a.P <= 0) return;
-  if (a.shs)
-    hipLaunchKernelGGL(preprocess_bwd_kernel<true>, dim3((a.P + 255) / 256), dim3(256), 0, s, a, cb);
-  else
-    hipLaunchKernelGGL(preprocess_bwd_kernel<false>, dim3((a.P + 255) / 256), dim3(256), 0, s, a, cb);
+  const dim3 grid((a.P + 255) / 256), block(256);
+  const bool win = cb.B > 1;  // B = 1: every frame is 0
+  if (a.shs && win) hipLaunchKernelGGL((preprocess_bwd_kernel<true, true>), grid, block, 0, s, a, cb);
+  else if (a.shs) hipLaunchKernelGGL((preprocess_bwd_kernel<true, false>), grid, block, 0, s, a, cb);
+  else if (win) hipLaunchKernelGGL((preprocess_bwd_kernel<false, true>), grid, block, 0, s, a, cb);
+  else hipLaunchKernelGGL((preprocess_bwd_kernel<false, false>), grid, block, 0, s, a, cb);
 }
 
 }  // namespace gs

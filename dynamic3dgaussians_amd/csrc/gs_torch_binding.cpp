@@ -17,6 +17,7 @@
 #include <string>
 #include <tuple>
 
+#include "gs_window.h"
 #include "gsplat_hip.h"
 
 namespace {
@@ -48,15 +49,22 @@ int feature_width(int64_t F) {
 struct Inputs {
   at::Device dev{at::kCUDA};
   int64_t P = 0, M = 0, F = 0, F_user = 0;
+  int64_t B = 1;  // frames per Gaussian in means3D (a temporal window, gs_window.h), else 1
   int D = 0;
   float scale_modifier = 1.f;
   Tensor means3D, colors, opacity, scales, rotations, cov3D, sh, sem;
   gs_gaussians g{};
 
   Inputs(const Tensor& means3D_, const OptT& colors_, const OptT& sem_, const OptT& opacity_, const OptT& scales_,
-         const OptT& rotations_, double scale_mod, const OptT& cov3D_, const OptT& sh_, int64_t degree) {
-    if (means3D_.dim() != 2 || means3D_.size(1) != 3)
+         const OptT& rotations_, double scale_mod, const OptT& cov3D_, const OptT& sh_, int64_t degree,
+         bool windowed = false) {
+    if (windowed) {
+      if (means3D_.dim() != 3 || means3D_.size(2) != 3)
+        throw std::runtime_error("means3D must have dimensions (num_points, frames, 3) with cam_frames");
+      B = means3D_.size(1);
+    } else if (means3D_.dim() != 2 || means3D_.size(1) != 3) {
       throw std::runtime_error("means3D must have dimensions (num_points, 3)");  // rasterize_points.cu:60-62
+    }
     dev = means3D_.device();
     P = means3D_.size(0);
     means3D = dev_f32(means3D_, dev, "means3D");
@@ -150,6 +158,23 @@ struct Cameras {
   }
 };
 
+// The temporal window of a call (gs_window.h): cam_frames empty = none.
+struct Window {
+  std::vector<int32_t> frames;
+  gs_window w{};
+  const gs_window* ptr = nullptr;
+  Window(const std::vector<int64_t>& cam_frames, int64_t C, int64_t B) {
+    if (cam_frames.empty()) return;
+    if ((int64_t)cam_frames.size() != C) throw std::runtime_error("cam_frames must have C entries");
+    frames.assign(cam_frames.begin(), cam_frames.end());
+    w.B = (int32_t)B;
+    w.cam_frame = frames.data();
+    ptr = &w;
+    check(gs_check_window(ptr, (int32_t)C), "camera frames");
+  }
+  Window(const Window&) = delete;
+};
+
 // capacity: empty = the two-phase path (plan, host read, render); else the
 // sync-free gs_forward_batch with a binning buffer of capacity[c] instances
 // per camera and `hint` (gs_batch_hint as {valid, p1, q1, p2, max_len,
@@ -157,6 +182,8 @@ struct Cameras {
 // reference's counts, the images and state, the exact num_instances, the
 // per-camera lengths the binning buffer is laid out with (what the backward
 // takes), the updated hint and whether the first attempt fitted.
+// cam_frames: empty = the call without a temporal window; else (gs_window.h)
+// means3D is (P, B, 3) and camera c renders frame cam_frames[c].
 std::tuple<std::vector<int64_t>, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, std::vector<int64_t>,
            std::vector<int64_t>, std::vector<int64_t>, bool>
 forward_batch(const Tensor& bg, const Tensor& means3D, const OptT& colors, const OptT& sem, const OptT& opacity,
@@ -166,8 +193,8 @@ forward_batch(const Tensor& bg, const Tensor& means3D, const OptT& colors, const
               int64_t degree, const Tensor& campos, bool prefiltered, bool debug, int64_t compat, bool activate,
               const std::vector<std::vector<int64_t>>& windows, int64_t feature_ready,
               const std::vector<int64_t>& capacity, const std::vector<int64_t>& hint, const OptT& walk_order,
-              const OptT& zero_fill, int64_t stream) {
-  Inputs in(means3D, colors, sem, opacity, scales, rotations, scale_modifier, cov3D, sh, degree);
+              const OptT& zero_fill, const std::vector<int64_t>& cam_frames, int64_t stream) {
+  Inputs in(means3D, colors, sem, opacity, scales, rotations, scale_modifier, cov3D, sh, degree, !cam_frames.empty());
   if (activate) in.g.flags |= GS_FLAG_ACTIVATE;
   in.g.feature_ready = reinterpret_cast<gs_event_t>(feature_ready);
   if (present(zero_fill)) {  // the backward's scratch, zeroed by the blend (gs_gaussians.zero_fill)
@@ -185,6 +212,7 @@ forward_batch(const Tensor& bg, const Tensor& means3D, const OptT& colors, const
   }
   Cameras k(in.dev, bg, views, projs, campos, cx, cy, tx, ty, W, H, windows);
   const int32_t C = (int32_t)k.cams.size();
+  const Window win(cam_frames, C, in.B);
   const auto f32 = at::TensorOptions().dtype(at::kFloat).device(in.dev);
   const auto u8 = at::TensorOptions().dtype(at::kByte).device(in.dev);
   Tensor out_color = at::empty({C, 3, H, W}, f32);
@@ -216,14 +244,15 @@ forward_batch(const Tensor& bg, const Tensor& means3D, const OptT& colors, const
     const int64_t nb = (int64_t)gs_batch_binning_buffer_bytes(C, capacity.data());
     binning = at::empty({nb > 1 ? nb : 1}, u8);
     int32_t fits = 0;
-    check(gs_forward_batch(&in.g, k.cams.data(), C, prefiltered ? 1 : 0, (int)compat, geom.data_ptr(),
-                           img.data_ptr(), binning.data_ptr(), capacity.data(), &h, radii.data_ptr<int32_t>(),
-                           NR.data(), NI.data(), &fits, oc, of, od, oa, s),
+    check(gs_forward_batch_window(&in.g, k.cams.data(), C, prefiltered ? 1 : 0, (int)compat, geom.data_ptr(),
+                                  img.data_ptr(), binning.data_ptr(), capacity.data(), &h,
+                                  radii.data_ptr<int32_t>(), NR.data(), NI.data(), &fits, oc, of, od, oa, win.ptr, s),
           "rasterize_gaussians_batch (sync-free forward)");
     fitted = fits != 0;
   } else {
-    check(gs_forward_plan_batch(&in.g, k.cams.data(), C, prefiltered ? 1 : 0, debug ? 1 : 0, (int)compat,
-                                geom.data_ptr(), img.data_ptr(), radii.data_ptr<int32_t>(), NR.data(), NI.data(), s),
+    check(gs_forward_plan_batch_window(&in.g, k.cams.data(), C, prefiltered ? 1 : 0, debug ? 1 : 0, (int)compat,
+                                       geom.data_ptr(), img.data_ptr(), radii.data_ptr<int32_t>(), NR.data(),
+                                       NI.data(), win.ptr, s),
           "rasterize_gaussians_batch (preprocess)");
   }
   std::vector<int64_t> layout = NI;
@@ -281,11 +310,13 @@ void set_densify(Inputs& in, const c10::optional<std::vector<Tensor>>& densify) 
 // entries) -- with `exact` each in its exact shape (the GradientSink
 // contract), else an empty entry = allocate and the others matched by element
 // count and viewed in their shapes (a gradient bucket's flat views).
-std::vector<Tensor> gradient_outputs(const Inputs& in, const std::vector<Tensor>& out, bool exact) {
+std::vector<Tensor> gradient_outputs(const Inputs& in, const std::vector<Tensor>& out, bool exact, bool windowed) {
   static const char* const names[9] = {"dmeans2D", "dcolors", "dsem", "dopacity", "dmeans3D",
                                        "dcov3D", "dsh", "dscales", "drot"};
   const int64_t P = in.P;
-  const std::vector<int64_t> shapes[9] = {{P, 3}, {P, 3}, {P, in.F}, {P, 1}, {P, 3}, {P, 6}, {P, in.M, 3}, {P, 3}, {P, 4}};
+  // dmeans3D of a temporal window: one row per frame, (P, B, 3)
+  const std::vector<int64_t> dmeans = windowed ? std::vector<int64_t>{P, in.B, 3} : std::vector<int64_t>{P, 3};
+  const std::vector<int64_t> shapes[9] = {{P, 3}, {P, 3}, {P, in.F}, {P, 1}, dmeans, {P, 6}, {P, in.M, 3}, {P, 3}, {P, 4}};
   if (!out.empty() && out.size() != 9) throw std::runtime_error("out must hold the 9 gradient buffers");
   std::vector<Tensor> o;
   for (int i = 0; i < 9; ++i) {
@@ -316,11 +347,11 @@ std::vector<Tensor> backward_batch(
     bool debug, int64_t compat, const OptT& grad_mask, c10::optional<std::vector<Tensor>> densify,
     const OptT& opacity, bool activate, const std::vector<std::vector<int64_t>>& windows,
     const std::vector<Tensor>& out, bool exact_out, bool accumulate, const OptT& scratch_in, bool scratch_zeroed,
-    int64_t stream) {
+    const std::vector<int64_t>& cam_frames, int64_t stream) {
   if (activate && !present(opacity)) throw std::runtime_error("activate=True needs the raw opacities");
   if (accumulate && out.empty()) throw std::runtime_error("accumulate needs the caller's gradient buffers");
   Inputs in(means3D, colors, sem, activate ? opacity : c10::nullopt, scales, rotations, scale_modifier, cov3D, sh,
-            degree);
+            degree, !cam_frames.empty());
   if (activate) in.g.flags |= GS_FLAG_ACTIVATE;
   if (accumulate) in.g.flags |= GS_FLAG_ACCUMULATE;
   const int64_t C = (int64_t)cx.size(), P = in.P;
@@ -329,6 +360,7 @@ std::vector<Tensor> backward_batch(
   const Tensor& img_ref = present(dL_color) ? *dL_color : alphas;
   const int64_t H = img_ref.size(-2), W = img_ref.size(-1);
   Cameras k(in.dev, bg, views, projs, campos, cx, cy, tx, ty, W, H, windows);
+  const Window win(cam_frames, C, in.B);
   Tensor gm;
   set_grad_mask(in, grad_mask, gm);
   Tensor dLc = batch_image(dL_color, C, 3, H, W, in.dev, "dL_dout_color");
@@ -340,7 +372,7 @@ std::vector<Tensor> backward_batch(
   if (radii_c.dim() != 2 || radii_c.size(0) != C || radii_c.size(1) != P)
     throw std::runtime_error("radii must be [C=" + std::to_string(C) + ", P=" + std::to_string(P) + "]");
   if ((int64_t)num_instances.size() != C) throw std::runtime_error("num_instances must have C entries");
-  std::vector<Tensor> o = gradient_outputs(in, out, exact_out);
+  std::vector<Tensor> o = gradient_outputs(in, out, exact_out, win.ptr != nullptr);
   set_densify(in, densify);
   // the scratch: the caller's (kept from the forward, which may have zeroed
   // it: scratch_zeroed -> GS_FLAG_SCRATCH_ZEROED) or a fresh one
@@ -356,12 +388,13 @@ std::vector<Tensor> backward_batch(
   }
   const Tensor bin = binning.has_value() ? *binning : Tensor();
   auto fp = [](const Tensor& t) -> const float* { return t.defined() ? t.data_ptr<float>() : nullptr; };
-  check(gs_backward_batch(&in.g, k.cams.data(), (int32_t)C, radii_c.data_ptr<int32_t>(), debug ? 1 : 0, (int)compat,
-                          geom.data_ptr(), nz(bin), img.data_ptr(), num_instances.data(), alphas_c.data_ptr<float>(),
-                          fp(dLc), fp(dLf), fp(dLd), fp(dLa), scratch.data_ptr(), o[0].data_ptr<float>(),
-                          o[1].data_ptr<float>(), static_cast<float*>(nz(o[2])), o[3].data_ptr<float>(),
-                          o[4].data_ptr<float>(), o[5].data_ptr<float>(), static_cast<float*>(nz(o[6])),
-                          o[7].data_ptr<float>(), o[8].data_ptr<float>(), reinterpret_cast<gs_stream_t>(stream)),
+  check(gs_backward_batch_window(&in.g, k.cams.data(), (int32_t)C, radii_c.data_ptr<int32_t>(), debug ? 1 : 0,
+                                 (int)compat, geom.data_ptr(), nz(bin), img.data_ptr(), num_instances.data(),
+                                 alphas_c.data_ptr<float>(), fp(dLc), fp(dLf), fp(dLd), fp(dLa), scratch.data_ptr(),
+                                 o[0].data_ptr<float>(), o[1].data_ptr<float>(), static_cast<float*>(nz(o[2])),
+                                 o[3].data_ptr<float>(), o[4].data_ptr<float>(), o[5].data_ptr<float>(),
+                                 static_cast<float*>(nz(o[6])), o[7].data_ptr<float>(), o[8].data_ptr<float>(), win.ptr,
+                                 reinterpret_cast<gs_stream_t>(stream)),
         "rasterize_gaussians_batch_backward");
   if (in.F_user != in.F) o[2] = o[2].narrow(1, 0, in.F_user);
   return o;

@@ -86,7 +86,8 @@ def _input_grads(grads, sem_shape, label, fuse):
         # __init__.py:159-173: every Gaussian-parameter gradient except
         # means2D and the semantic feature is masked by `label` (Q12).
         lab = label.unsqueeze(1)
-        grad_means3D = grad_means3D * lab
+        # a temporal window's (P, B, 3) mean gradient: the label spans the frames
+        grad_means3D = grad_means3D * (lab[..., None] if grad_means3D.dim() == 3 else lab)
         grad_sh = grad_sh * lab[..., None]
         grad_colors_precomp = grad_colors_precomp * lab
         grad_opacities = grad_opacities * lab
@@ -447,7 +448,7 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, semantic_feature, opacities, scales, rotations,
                 cov3Ds_precomp, cams, label, densify_out, raw_params=False, feature_ready=None, plan_state=None,
-                grad_into=None, walk_order=None):
+                grad_into=None, walk_order=None, camera_frames=None):
         if not isinstance(cams, _BatchCameras):
             cams = _BatchCameras(cams)
         rs0 = cams.rs0
@@ -469,7 +470,8 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
             cov3Ds_precomp, views, projs, [p[0] for p in pp], [p[1] for p in pp], tx, ty, rs0.image_height,
             rs0.image_width, sh, rs0.sh_degree, cpos, rs0.prefiltered, rs0.debug, compat=compat,
             activate=raw_params, windows=cams.windows, feature_ready=feature_ready, plan_state=plan_state,
-            walk_order=walk_order, zero_fill=scratch)
+            walk_order=walk_order, zero_fill=scratch, cam_frames=camera_frames)
+        ctx.camera_frames = camera_frames
         ctx.scratch, ctx.scratch_zeroed = scratch, scratch is not None
         num_rendered, color, feature_map, depth, alpha, radii, geom, binning, img, num_instances = out
         ctx.rs0 = rs0
@@ -508,12 +510,12 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
             rs0.sh_degree, cpos, geom, ctx.num_instances, binning, img, alpha, rs0.debug, compat=ctx.compat,
             grad_mask=label if fuse else None, densify=ctx.densify_out, opacity=raw_opacities,
             activate=ctx.raw_params, windows=windows, out=ctx.grad_into, scratch=ctx.scratch,
-            scratch_zeroed=ctx.scratch_zeroed)
+            scratch_zeroed=ctx.scratch_zeroed, cam_frames=ctx.camera_frames)
         ctx.scratch_zeroed = False  # a second backward (retain_graph) finds it written
         if label is not None and not fuse and ctx.raw_params:
             raise RuntimeError("raw_params=True needs a per-Gaussian fp32 label (or none): the mask is "
                                "applied in-kernel before the activations' backward")
-        grads = _input_grads(grads, ctx.sem_shape, label, fuse) + (None,) * 8
+        grads = _input_grads(grads, ctx.sem_shape, label, fuse) + (None,) * 9
         # gradients written into caller-owned destinations: autograd gets None
         taken = [False] * len(grads)
         for k in (ctx.grad_into or {}):
@@ -545,7 +547,8 @@ def _grad_destinations(grad_into, semantic_feature):
 
 def rasterize_gaussians_batch(means3D, means2D, sh, colors_precomp, semantic_feature, opacities, scales,
                               rotations, cov3Ds_precomp, settings_list, label=None, densify_out=None,
-                              raw_params=False, feature_ready=None, plan_state=None, grad_into=None, walk_order=None):
+                              raw_params=False, feature_ready=None, plan_state=None, grad_into=None, walk_order=None,
+                              camera_frames=None):
     """rasterize_gaussians over a list of camera settings; outputs [C, ...]
     (color, radii, feature_map, depth, alpha).  `densify_out`: optional
     (accum, denom, max_radius) fp32 [P] tensors the backward fills with the
@@ -563,11 +566,31 @@ def rasterize_gaussians_batch(means3D, means2D, sh, colors_precomp, semantic_fea
     autograd None for them, so no gradient tensor is allocated, accumulated
     or copied into a bucket; gradients reaching those tensors through other
     autograd paths are not added.  `walk_order`: the binning passes' walk
-    order (_C.spatial_order; outputs do not depend on it)."""
+    order (_C.spatial_order; outputs do not depend on it).  `camera_frames`:
+    a temporal window (GaussianRasterizerBatch; include/gs_window.h) -- C
+    non-decreasing frame indices; means3D is (P, B, 3) and its gradient too."""
     cams = settings_list if isinstance(settings_list, _BatchCameras) else _BatchCameras(list(settings_list))
     return _RasterizeGaussiansBatch.apply(means3D, means2D, sh, colors_precomp, semantic_feature, opacities,
                                           scales, rotations, cov3Ds_precomp, cams, label, densify_out,
-                                          bool(raw_params), feature_ready, plan_state, grad_into, walk_order)
+                                          bool(raw_params), feature_ready, plan_state, grad_into, walk_order,
+                                          camera_frames)
+
+
+def _check_frames(camera_frames, C):
+    """A temporal window's per-camera frames as a list of C ints, validated
+    (include/gs_window.h gs_check_window's rules), or None."""
+    if camera_frames is None:
+        return None
+    frames = [int(f) for f in camera_frames]
+    if len(frames) != C:
+        raise ValueError(f"camera_frames has {len(frames)} entries for {C} cameras")
+    if any(f < 0 for f in frames):
+        raise ValueError(f"camera_frames must be >= 0, got {frames}")
+    if any(b < a for a, b in zip(frames, frames[1:])):
+        raise ValueError(f"camera_frames must be non-decreasing (sort the cameras by frame), got {frames}")
+    if frames and frames[-1] >= _lib.GS_WINDOW_MAX_FRAMES:
+        raise ValueError(f"camera_frames: at most {_lib.GS_WINDOW_MAX_FRAMES} frames per window, got frame {frames[-1]}")
+    return frames
 
 
 class GaussianRasterizerBatch(nn.Module):
@@ -603,12 +626,26 @@ class GaussianRasterizerBatch(nn.Module):
     previous call's lists outgrow the bucket pass's LDS staging (large
     scenes, e.g. BASELINE configs[4]); False -- id order.  Outputs are
     bit-identical either way (every tile list is sorted by its unique
-    (depth bits, id) keys)."""
+    (depth bits, id) keys).
+
+    `camera_frames` (a sequence of C ints, non-decreasing): a temporal window
+    (include/gs_window.h) -- the cameras of several frames of a motion model
+    in one batch.  `means3D` is then (P, B, 3), fp32 and contiguous, the
+    layout MotionBases.compute_means returns, and camera c is rendered at
+    means3D[:, camera_frames[c]] exactly as a batch over that frame's means
+    would render it; every other input is shared by the frames.
+    means3D.grad is (P, B, 3): frame b holds the sum over the cameras of
+    frame b (zeros for a frame no camera uses), every other gradient and the
+    `track_densify` statistics are summed over all cameras of all frames (a
+    Gaussian seen from two frames counts twice in `denom`).  Sort the cameras
+    by frame; outputs are stacked in the given camera order.  The Morton walk
+    (`spatial_order`) is taken from the first camera's frame."""
 
     def __init__(self, settings_list, track_densify=False, raw_params=False, sync_free=True, spatial_order="auto",
-                 order_refresh=256):
+                 order_refresh=256, camera_frames=None):
         super().__init__()
         self.settings_list = list(settings_list)
+        self.camera_frames = _check_frames(camera_frames, len(self.settings_list))
         self.plan = _C.BinningPlan() if sync_free else None
         if spatial_order not in (True, False, "auto"):
             raise ValueError("spatial_order: True, False or 'auto'")
@@ -653,7 +690,9 @@ class GaussianRasterizerBatch(nn.Module):
             return None
         if (self._walk is None or self._walk.numel() != means3D.size(0)
                 or self._walk_calls % self.order_refresh == 0):
-            self._walk = _C.spatial_order(means3D)
+            # a temporal window: the first camera's frame (a copy, on refresh only)
+            self._walk = _C.spatial_order(means3D if self.camera_frames is None
+                                          else means3D[:, self.camera_frames[0]])
         self._walk_calls += 1
         return self._walk
 
@@ -666,6 +705,13 @@ class GaussianRasterizerBatch(nn.Module):
         optional): {argument name: tensor} destinations the backward writes
         those gradients into (rasterize_gaussians_batch)."""
         _check_inputs(shs, colors_precomp, scales, rotations, cov3D_precomp)
+        if self.camera_frames is not None:
+            if means3D.dim() != 3 or means3D.size(2) != 3 or means3D.size(1) <= self.camera_frames[-1]:
+                raise ValueError(f"camera_frames: means3D must be (P, B, 3) with B > {self.camera_frames[-1]}, got "
+                                 f"{tuple(means3D.shape)}")
+            if means3D.dtype != torch.float32 or not means3D.is_contiguous():
+                raise ValueError("camera_frames: means3D must be fp32 and contiguous (Gaussian-major, the layout "
+                                 "MotionBases.compute_means returns)")
         shs, colors_precomp, scales, rotations, cov3D_precomp = map(
             _empty_like_none, (shs, colors_precomp, scales, rotations, cov3D_precomp))
         has_label = label is not _UNSET
@@ -678,5 +724,5 @@ class GaussianRasterizerBatch(nn.Module):
         out = rasterize_gaussians_batch(
             means3D, means2D, shs, colors_precomp, semantic_feature, opacities, scales, rotations,
             cov3D_precomp, self._cams, lab, dens, self.raw_params, feature_ready, self.plan, grad_into,
-            self._walk_order(means3D))
+            self._walk_order(means3D), self.camera_frames)
         return _by_generation(has_label, semantic_feature is not None, *out)

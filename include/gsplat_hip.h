@@ -242,7 +242,10 @@ int gs_backward(const gs_gaussians *g, const gs_camera *cam, const int32_t *radi
  *    24 B per tile instance.  At P = 300k, C = 27 the scratch is 518 MB and
  *    the fill ~0.1 ms per step; at P = 1M, C = 64 it is 4.1 GB -- split
  *    larger rigs into camera groups of one batch call each (the gradients
- *    of successive calls add with GS_FLAG_ACCUMULATE). */
+ *    of successive calls add with GS_FLAG_ACCUMULATE).
+ *  - Temporal windows (the cameras of several frames of a motion model in one
+ *    batch, means3D P x B x 3): gs_window.h, the *_window forms of the plan,
+ *    sync-free forward and backward calls below. */
 size_t gs_batch_geom_buffer_bytes(int64_t P, int32_t C);
 size_t gs_batch_image_buffer_bytes(int32_t W, int32_t H, int32_t C);
 size_t gs_batch_binning_buffer_bytes(int32_t C, const int64_t *num_instances);
