@@ -29,14 +29,15 @@ struct AdamTable {
   gs_densify_stats st;
 };
 
-// torch's lerp (exp_avg.lerp_(grad, 1 - beta1), weight < 0.5), mul,
+// torch's lerp (exp_avg.lerp_(grad, 1 - beta1): a + w (b - a) for a weight
+// below 0.5, b - (b - a)(1 - w) from 0.5 up, i.e. beta1 <= 0.5), mul,
 // addcmul, sqrt, div, add and addcdiv of _multi_tensor_adam, in the same
 // order and with the multiply-adds torch's ROCm build contracts written as
 // explicit fmas (this file is built with -ffp-contract=off, so nothing else
 // is fused).
 __device__ inline void adam1(float& p, float g, float& m, float& v, float w1, float b2, float om_b2, float eps,
                              float step_size, float bc2s) {
-  m = fmaf(w1, g - m, m);
+  m = fabsf(w1) < 0.5f ? fmaf(w1, g - m, m) : fmaf(-(g - m), 1.f - w1, g);
   v = fmaf(om_b2, g * g, v * b2);
   const float denom = sqrtf(v) / bc2s + eps;
   p = fmaf(step_size, m / denom, p);

@@ -101,3 +101,72 @@ def test_knn_edge_cases_and_dropins():
     assert means.dtype == torch.float32 and nn.dtype == torch.int32 and nn.shape == (2000, 3)
     np.testing.assert_allclose(means.cpu().numpy(), od.mean(1), rtol=1e-6)
     np.testing.assert_array_equal(nn.cpu().numpy(), oi)
+
+
+# ---- template boundaries (knn_query_kernel<4 | 8 | 16 | 20 | 32>), the
+# 256-point box boundary, N <= K and clouds whose Morton code degenerates
+
+DEV = "cuda"
+
+
+def _assert_knn_exact(p, k):
+    """Bit-exact against the oracle; rows with fewer than k other points end
+    in (+inf, -1) after the exact valid prefix."""
+    from dynamic3dgaussians_amd.knn import knn
+    N = p.shape[0]
+    d, i = knn(torch.from_numpy(p).to(DEV), k)
+    d, i = d.cpu().numpy(), i.cpu().numpy()
+    assert d.shape == (N, k) and i.shape == (N, k) and d.dtype == np.float64 and i.dtype == np.int64
+    m = min(k, N - 1)
+    od, oi = ON.knn(p, m)
+    np.testing.assert_array_equal(d[:, :m], od)
+    np.testing.assert_array_equal(i[:, :m], oi)
+    assert np.isposinf(d[:, m:]).all() and (i[:, m:] == -1).all()
+
+
+@pytest.mark.gpu
+# N: one box less a point | one full box | two boxes, one point in the second | three boxes
+# k: both sides of every template (4|5, 8|9, 16|17, 20|21) and the widest
+@pytest.mark.parametrize("N", [255, 256, 257, 513])
+@pytest.mark.parametrize("k", [4, 5, 8, 9, 16, 17, 20, 21, 32])
+def test_knn_template_and_box_boundaries(N, k):
+    _assert_knn_exact(_cloud(N, "clusters", seed=N + k), k)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("N", [1, 2, 9, 20])
+@pytest.mark.parametrize("k", [8, 20, 32])  # knn_query_kernel<8 | 20 | 32>: slots >= N - 1 stay (+inf, -1)
+def test_knn_fewer_points_than_k(N, k):
+    _assert_knn_exact(_cloud(N, "uniform", seed=N + k), k)
+
+
+def _degenerate(kind, N=600):
+    g = np.random.default_rng(11)
+    if kind == "identical":  # extent 0 on every axis: every Morton code 0, ties by index across 3 boxes
+        p = np.tile(np.array([[0.25, -1.5, 3.0]]), (N, 1))
+    elif kind == "half_identical":  # 300 copies of one point + 300 uniform points
+        p = g.random((N, 3))
+        p[::2] = p[0]
+    elif kind == "collinear":  # two zero extents, 40 grid positions: ~15 exact copies of each
+        p = np.stack([g.integers(0, 40, N) * 0.05, np.zeros(N), np.zeros(N)], 1)
+    elif kind == "offset":  # fp32 spacing at 1e4 is 2^-10: coordinates collapse to 1024 values per axis
+        p = g.random((N, 3)) + np.array([1e4, -1e4, 1e4])
+    else:
+        raise ValueError(kind)
+    return p.astype(np.float32)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind", ["identical", "half_identical", "collinear", "offset"])
+@pytest.mark.parametrize("k", [3, 20])
+def test_knn_degenerate_clouds(kind, k):
+    _assert_knn_exact(_degenerate(kind), k)
+
+
+@pytest.mark.gpu
+def test_distcuda2_identical_points():
+    from dynamic3dgaussians_amd.knn import distCUDA2
+    p = _degenerate("identical")
+    means, nn = distCUDA2(torch.from_numpy(p).to(DEV))
+    assert torch.equal(means, torch.zeros(600, device=DEV))  # mean 0, not NaN
+    np.testing.assert_array_equal(nn.cpu().numpy(), ON.knn(p, 3)[1])
