@@ -441,6 +441,43 @@ def rasterize_gaussians_batch_backward(background, means3D, radii, colors, seman
                      scratch_zeroed=scratch_zeroed, cam_frames=cam_frames)
 
 
+camera_grad_calls = 0  # camera-gradient launches so far (tests: none without a camera tensor that requires grad)
+
+
+def rasterize_gaussians_batch_camera_grad(background, means3D, radii, cov3D_precomp, viewmatrices, projmatrices,
+                                          c_x, c_y, tan_fovx, tan_fovy, image_height, image_width, sh, degree,
+                                          campos, geomBuffer, scratch, *, compat=None, windows=None,
+                                          cam_frames=None):
+    """The gradients of a camera batch's matrices and positions
+    (gs_camera_grad_batch, include/gs_camera_grad.h), to be called after
+    rasterize_gaussians_batch_backward on the same stream with the same
+    inputs and the `scratch` that call was given (its accumulation records
+    are read).  Returns (dL_dviewmatrices [C,16], dL_dprojmatrices [C,16],
+    dL_dcampos [C,3]): the exact derivative of the compat="fixed" forward;
+    compat="reference" is refused.  The tan(fov/2) and principal-point
+    scalars are not differentiated.  With tile `windows` the gradient is that
+    of the windows' pixels."""
+    global camera_grad_calls
+    cm = _compat_code(compat)
+    if cm != _lib.GS_COMPAT["fixed"]:
+        raise ValueError('camera gradients need compat="fixed": the reference-mode backward is not the derivative '
+                         'of its forward')
+    C = len(c_x)
+    if _num_points(means3D, cam_frames is not None) == 0:  # answered like the forward and the backward
+        f32 = dict(dtype=torch.float32, device=means3D.device)
+        return torch.zeros(C, 16, **f32), torch.zeros(C, 16, **f32), torch.zeros(C, 3, **f32)
+    camera_grad_calls += 1
+    try:
+        return tuple(_native_mod().camera_grad_batch(
+            background, means3D, radii, _opt(cov3D_precomp) if _present(cov3D_precomp) else None, viewmatrices,
+            projmatrices, [float(x) for x in c_x], [float(x) for x in c_y], [float(x) for x in tan_fovx],
+            [float(x) for x in tan_fovy], int(image_height), int(image_width), _opt(sh) if _present(sh) else None,
+            int(degree), campos, geomBuffer, scratch, cm, _windows_arg(windows), _frames_arg(cam_frames),
+            _lib.stream(means3D.device)))
+    except RuntimeError as ex:
+        raise _lib.GsplatError(str(ex)) from None
+
+
 def _backward(background, means3D, radii, colors, semantic_feature, scales, rotations, scale_modifier,
               cov3D_precomp, viewmatrices, projmatrices, c_x, c_y, tan_fovx, tan_fovy, dL_dout_color,
               dL_dout_feature, dL_dout_depth, dL_dout_alpha, sh, degree, campos, geomBuffer, num_instances,

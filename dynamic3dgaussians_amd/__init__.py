@@ -7,7 +7,8 @@ Layout:
   _lib.py         loads the library: ctypes mirrors of the C ABI (fails loudly; no CPU fallback)
   _C.py           positional mirror of the reference pybind module `_C`, over csrc/gs_torch_binding.cpp
   rasterizer.py   autograd boundary (GaussianRasterizer & friends)
-  camera.py       helpers.setup_camera restatement + synthetic camera rig
+  camera.py       helpers.setup_camera restatement + synthetic camera rig + PoseRefiner (trainable poses for the
+                  rasterizer's differentiable camera tensors, include/gs_camera_grad.h)
   scene.py        synthetic scenes for tests and the benchmark
   distributed.py  camera-sharded data parallelism with one RCCL all-reduce
   image_loss.py   the reference's L1 + SSIM photometric loss, fused (include/gs_loss.h)
@@ -17,7 +18,8 @@ Layout:
   densify.py      the reference's clone / split / prune with the Adam state (include/gs_densify.h)
   scene_loss.py   the reference's floor / bg / soft_col_cons terms and its foreground split, no host syncs
                   (include/gs_scene_loss.h)
-  metrics.py      the reference's quality reports: masked PSNR, masked SSIM, mask IoU (include/gs_metrics.h)
+  metrics.py      the reference's quality reports: masked PSNR, masked SSIM, mask IoU (include/gs_metrics.h),
+                  pose errors
   motion.py       the reference's motion-basis warp: SE(3) basis blend, fused (include/gs_motion.h)
 """
 from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, GradientSink,  # noqa: F401
@@ -34,7 +36,8 @@ from .scene_loss import (foreground_split, gather_foreground, reference_extra_lo
                          regularizer_losses_torch)
 from .metrics import (ImageMetrics, MaskedPSNR, MaskedSSIM, MaskIoU, MeanIoU, evaluate_cameras,  # noqa: F401
                       evaluate_sequence, image_metrics, image_metrics_torch, iou, mask_iou, mask_iou_torch,
-                      psnr_clamped, psnr_masked, psnr_plain)
+                      pose_errors, psnr_clamped, psnr_masked, psnr_plain)
+from .camera import PoseRefiner  # noqa: F401
 from .motion import (MotionBases, cont_6d_to_rmat, motion_positions, motion_positions_torch,  # noqa: F401
                      motion_transforms)
 

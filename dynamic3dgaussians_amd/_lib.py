@@ -163,6 +163,7 @@ class GsBatchHint(ctypes.Structure):
 
 
 GS_WINDOW_MAX_FRAMES = 64  # include/gs_window.h
+GS_CAMERA_GRAD_MAX_CAMS = 64  # include/gs_camera_grad.h
 
 
 class GsWindow(ctypes.Structure):
@@ -227,6 +228,12 @@ PROTOTYPES = {
                                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                 c_void_p, P_W, c_void_p]),
+    # include/gs_camera_grad.h
+    "gs_camera_grad_workspace_bytes": (c_size_t, [c_int64, c_int32]),
+    "gs_check_camera_grad": (ctypes.c_int, [c_int64, c_int32, ctypes.c_int, c_void_p, ctypes.c_uint64, c_void_p,
+                                            c_void_p, c_void_p]),
+    "gs_camera_grad_batch": (ctypes.c_int, [P_G, P_C, c_int32, P_W, c_void_p, ctypes.c_int, c_void_p, c_void_p,
+                                            c_void_p, ctypes.c_uint64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gs_mark_visible": (ctypes.c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gs_debug_export": (ctypes.c_int, [c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
                                        c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

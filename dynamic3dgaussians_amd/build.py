@@ -71,6 +71,7 @@ SOURCES = {
     "gs_resample.hip": [],
     "gs_scene_loss.hip": ["-ffp-contract=off"],  # act_normalize in the preprocess kernels' order
     "gs_metrics.hip": ["-ffp-contract=off"],  # the SSIM map of pred == target is 1 exactly
+    "gs_camera_grad.hip": ["-ffp-contract=off"],  # the per-pair terms in preprocess_bwd's operation order
     "gs_api.hip": [],
     "gs_host.cpp": [],  # host-only C++ (also built by oracle/Makefile's sanitizer target)
     "gs_densify_host.cpp": [],  # host-only C++ (also built into tools/densify_host_sanitize.c's program)
@@ -81,6 +82,7 @@ SOURCES = {
     "gs_scene_loss_host.cpp": [],  # host-only C++ (also built into tools/scene_loss_host_sanitize.c's program)
     "gs_metrics_host.cpp": [],  # host-only C++ (also built into tools/metrics_host_sanitize.c's program)
     "gs_window_host.cpp": [],  # host-only C++ (also built into tools/window_host_sanitize.c's program)
+    "gs_camera_grad_host.cpp": [],  # host-only C++ (also built into tools/camera_grad_host_sanitize.c's program)
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall",
           "-Wno-unused-function", "-I", CSRC, "-I", INCLUDE]

@@ -5,7 +5,9 @@ intrinsics K and a world-to-camera matrix become the raster settings the
 rasterizer consumes (column-major view / full-projection matrices, tan(fov/2),
 principal point).  The reference module imports open3d at module level, so it
 is restated rather than imported.  Also provides the synthetic camera rig the
-benchmark uses: cameras on a ring/dome looking at the origin.
+benchmark uses: cameras on a ring/dome looking at the origin,
+and PoseRefiner, the pose parameterisation whose output feeds the rasterizer's
+differentiable camera tensors.
 """
 from __future__ import annotations
 
@@ -13,6 +15,7 @@ import math
 from dataclasses import dataclass
 
 import numpy as np
+import torch
 
 
 @dataclass
@@ -44,6 +47,69 @@ def setup_camera(w, h, k, w2c, near=0.01, far=100.0) -> CameraParams:
     return CameraParams(W=int(w), H=int(h), viewmatrix=view, projmatrix=full_proj,
                         campos=cam_center, c_x=float(cx), c_y=float(cy),
                         tanfovx=float(w / (2 * fx)), tanfovy=float(h / (2 * fy)))
+
+
+class PoseRefiner(torch.nn.Module):
+    """Trainable camera poses for GaussianRasterizerBatch's differentiable
+    camera tensors (no reference analogue: the reference's poses are inputs).
+
+    `w2c` [C, 4, 4] are the initial world-to-camera matrices, `K` [C, 3, 3] (or
+    one [3, 3] for all) the OpenCV intrinsics of a W x H image.  The
+    parameters `rot` and `trans` ([C, 3], zero-initialised) form a
+    camera-frame twist whose exponential left-multiplies w2c:
+
+        w2c' = exp([[hat(rot), trans], [0, 0]]) @ w2c
+
+    (torch.linalg.matrix_exp: differentiable at zero twist, where a
+    sin(theta) / theta form is not).  forward() returns (viewmatrices,
+    projmatrices, campos) in exactly setup_camera's layout and conventions --
+    view = w2c'^T, proj = view @ opengl_proj^T, campos = -R'^T t' -- to pass as
+    GaussianRasterizerBatch.forward(..., viewmatrices=, projmatrices=,
+    campos=).  The intrinsics are constants: build the raster settings
+    (tanfovx / tanfovy, c_x / c_y) from the same K with setup_camera.
+    poses() returns the refined camera-to-world matrices (metrics.pose_errors).
+    The buffers follow the module's dtype (.double() for gradient checks)."""
+
+    def __init__(self, w2c, K, W, H, near=0.01, far=100.0):
+        super().__init__()
+        w2c = torch.as_tensor(np.asarray(w2c, dtype=np.float64)).reshape(-1, 4, 4)
+        C = w2c.shape[0]
+        K = torch.as_tensor(np.asarray(K, dtype=np.float64)).reshape(-1, 3, 3).expand(C, 3, 3)
+        fx, fy, cx, cy = K[:, 0, 0], K[:, 1, 1], K[:, 0, 2], K[:, 1, 2]
+        proj = torch.zeros(C, 4, 4, dtype=torch.float64)  # helpers.py:79-82 opengl_proj
+        proj[:, 0, 0], proj[:, 0, 2] = 2 * fx / W, -(W - 2 * cx) / W
+        proj[:, 1, 1], proj[:, 1, 2] = 2 * fy / H, -(H - 2 * cy) / H
+        proj[:, 2, 2], proj[:, 2, 3] = far / (far - near), -(far * near) / (far - near)
+        proj[:, 3, 2] = 1.0
+        self.register_buffer("w2c", w2c.float())
+        self.register_buffer("c2w", torch.linalg.inv(w2c.float().double()).float())  # of the fp32 w2c, once, on the host
+        self.register_buffer("proj_t", proj.transpose(1, 2).contiguous().float())
+        self.rot = torch.nn.Parameter(torch.zeros(C, 3))
+        self.trans = torch.nn.Parameter(torch.zeros(C, 3))
+
+    def _twist(self) -> torch.Tensor:
+        r, t = self.rot, self.trans
+        xi = r.new_zeros(r.shape[0], 4, 4)
+        xi[:, 0, 1], xi[:, 0, 2], xi[:, 1, 2] = -r[:, 2], r[:, 1], -r[:, 0]
+        xi[:, 1, 0], xi[:, 2, 0], xi[:, 2, 1] = r[:, 2], -r[:, 1], r[:, 0]
+        xi[:, :3, 3] = t
+        return xi
+
+    def refined_w2c(self) -> torch.Tensor:
+        """[C, 4, 4]: the twist's exponential times the initial w2c."""
+        return torch.linalg.matrix_exp(self._twist()) @ self.w2c
+
+    def forward(self):
+        w2c = self.refined_w2c()
+        view = w2c.transpose(1, 2).contiguous()
+        proj = view @ self.proj_t
+        campos = -(w2c[:, :3, :3].transpose(1, 2) @ w2c[:, :3, 3:4]).squeeze(-1)
+        return view, proj, campos
+
+    def poses(self) -> torch.Tensor:
+        """[C, 4, 4] camera-to-world, the inverse of the refined w2c: the
+        initial inverse times the exponential of the negated twist."""
+        return self.c2w @ torch.linalg.matrix_exp(-self._twist())
 
 
 def look_at_w2c(eye, target=(0.0, 0.0, 0.0), up=(0.0, 1.0, 0.0)) -> np.ndarray:

@@ -16,6 +16,7 @@
 #include <thread>
 #include <vector>
 
+#include "../../include/gs_camera_grad.h"
 #include "../../include/gs_window.h"
 #include "../../include/gsplat_hip.h"
 #include "gs_common.h"
@@ -934,6 +935,46 @@ int gs_backward_batch(const gs_gaussians* g, const gs_camera* cams, int32_t C, c
                                   dL_dout_color, dL_dout_feature, dL_dout_depth, dL_dout_alpha, scratch,
                                   dL_dmeans2D, dL_dcolors, dL_dsemantic, dL_dopacity, dL_dmeans3D, dL_dcov3D,
                                   dL_dsh, dL_dscales, dL_drotations, nullptr, stream);
+}
+
+// ---- camera gradients (include/gs_camera_grad.h): after the batch backward,
+// from the accumulation records it left in its scratch (preprocess_bwd reads
+// them const, nothing after the blend backward writes them)
+int gs_camera_grad_batch(const gs_gaussians* g, const gs_camera* cams, int32_t C, const gs_window* win,
+                         const int32_t* radii, int compat, const void* geom, const void* scratch, void* workspace,
+                         uint64_t workspace_bytes, float* dL_dview, float* dL_dproj, float* dL_dcampos,
+                         gs_stream_t stream) {
+  if (!g || !cams) return fail(-1, "null argument block");
+  if (int e = gs_check_camera_grad(g->P, C, compat, workspace, workspace_bytes, dL_dview, dL_dproj, dL_dcampos))
+    return e;
+  hipStream_t s = (hipStream_t)stream;
+  const int P = g->P;
+  CameraGradArgs a{};
+  a.P = P;
+  a.records = static_cast<double*>(workspace);
+  a.dview = dL_dview; a.dproj = dL_dproj; a.dcampos = dL_dcampos;
+  CamBatch cb{};
+  cb.C = C;
+  if (P > 0) {
+    if (!geom || !scratch || !radii) return fail(-1, "camera grad: state buffers are required");
+    if (!g->means3D || !cams[0].viewmatrix || !cams[0].projmatrix || !cams[0].campos)
+      return fail(-1, "camera grad: means3D, camera matrices and campos are required");
+    if (g->shs && (g->D < 0 || g->D > 3 || g->M < (g->D + 1) * (g->D + 1)))
+      return fail(-1, "SH degree %d needs M >= %d coefficients (got M=%d)", g->D, (g->D + 1) * (g->D + 1), g->M);
+    const int W = cams[0].image_width, H = cams[0].image_height;
+    if (W <= 0 || H <= 0) return fail(-1, "image size must be positive (got %dx%d)", W, H);
+    if (int e = make_batch(cams, C, P, W, H, cb, win)) return e;
+    const GeomLayout gl(P);
+    a.D = g->D; a.M = g->M; a.W = W; a.H = H;
+    a.means3D = g->means3D; a.radii = radii; a.shs = g->shs;
+    a.clamped = at<uint8_t>(geom, gl.clamped);
+    a.cov3D = at<float>(geom, gl.cov3D);
+    a.cov3D_precomp = g->cov3D_precomp;
+    a.rec = at<float>(geom, gl.rec);
+    a.acc = static_cast<const float*>(scratch);
+  }
+  launch_camera_grad(a, cb, s);
+  return launch_status("camera grad", 0, s);
 }
 
 int gs_mark_visible(int64_t P, const float* means3D, const float* viewmatrix, const float* projmatrix,

@@ -148,6 +148,26 @@ void launch_preprocess_fwd(const PreprocessArgs& a, const CamBatch& cb, hipStrea
 void launch_preprocess_bwd(const PreprocessBwdArgs& a, const CamBatch& cb, hipStream_t s);
 void launch_mark_visible(int P, const float* means3D, const float* view, uint8_t* present, hipStream_t s);
 
+// Camera gradients (gs_camera_grad.hip, include/gs_camera_grad.h): the state
+// preprocess_bwd reads, reduced over the Gaussians per camera.
+struct CameraGradArgs {
+  int P, D, M, W, H;
+  const float* means3D;
+  const int* radii;            // C x P
+  const float* shs;            // or null (precomputed colours: dcampos = 0)
+  const uint8_t* clamped;      // camera 0's; per camera at geom_stride
+  const float* cov3D;          // the forward's (geometry buffer of camera 0)
+  const float* cov3D_precomp;  // the caller's, or null
+  const float* rec;            // camera 0's P x REC render records (conic); per camera at geom_stride
+  const float* acc;            // C x P x ACC_STRIDE blend gradient sums, as the backward left them
+  double* records;             // C x chunks x CG_REC (gs_camera_grad_layout.h)
+  float* dview;                // C x 16
+  float* dproj;                // C x 16
+  float* dcampos;              // C x 3
+};
+// P = 0: only the finishing kernel runs (zeros); cb is then read for C alone
+void launch_camera_grad(const CameraGradArgs& a, const CamBatch& cb, hipStream_t s);
+
 // Stable LSD radix sort on bits [0, end_bit) (the standalone gs_sort_pairs
 // entry point); the result ends in keys0/vals0 or keys1/vals1 -- returns 0
 // or 1 for which (passes of 8 bits swap slots).

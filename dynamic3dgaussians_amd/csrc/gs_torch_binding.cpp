@@ -17,6 +17,7 @@
 #include <string>
 #include <tuple>
 
+#include "gs_camera_grad.h"
 #include "gs_window.h"
 #include "gsplat_hip.h"
 
@@ -400,6 +401,41 @@ std::vector<Tensor> backward_batch(
   return o;
 }
 
+// The gradients of the C cameras (gs_camera_grad.h), after backward_batch on
+// the same stream with the same inputs, from the `scratch` that call wrote:
+// (dL_dview [C,16], dL_dproj [C,16], dL_dcampos [C,3]).
+std::tuple<Tensor, Tensor, Tensor> camera_grad_batch(
+    const Tensor& bg, const Tensor& means3D, const Tensor& radii, const OptT& cov3D, const Tensor& views,
+    const Tensor& projs, const std::vector<double>& cx, const std::vector<double>& cy, const std::vector<double>& tx,
+    const std::vector<double>& ty, int64_t H, int64_t W, const OptT& sh, int64_t degree, const Tensor& campos,
+    const Tensor& geom, const Tensor& scratch, int64_t compat, const std::vector<std::vector<int64_t>>& windows,
+    const std::vector<int64_t>& cam_frames, int64_t stream) {
+  Inputs in(means3D, c10::nullopt, c10::nullopt, c10::nullopt, c10::nullopt, c10::nullopt, 1.0, cov3D, sh, degree,
+            !cam_frames.empty());
+  const int64_t C = (int64_t)cx.size(), P = in.P;
+  Cameras k(in.dev, bg, views, projs, campos, cx, cy, tx, ty, W, H, windows);
+  const Window win(cam_frames, C, in.B);
+  Tensor radii_c = radii.to(in.dev, at::kInt).contiguous();
+  if (P > 0 && (radii_c.dim() != 2 || radii_c.size(0) != C || radii_c.size(1) != P))
+    throw std::runtime_error("radii must be [C=" + std::to_string(C) + ", P=" + std::to_string(P) + "]");
+  if (P > 0) {
+    const int64_t nscr = (int64_t)gs_batch_backward_scratch_bytes(P, 0, (int32_t)C);
+    if (scratch.device() != in.dev || !scratch.is_contiguous() || scratch.numel() * scratch.element_size() < nscr ||
+        geom.device() != in.dev || geom.numel() < (int64_t)gs_batch_geom_buffer_bytes(P, (int32_t)C))
+      throw std::runtime_error("camera_grad_batch: geom and scratch must be the forward's and the backward's buffers");
+  }
+  const auto f32 = at::TensorOptions().dtype(at::kFloat).device(in.dev);
+  Tensor dview = at::empty({C, 16}, f32), dproj = at::empty({C, 16}, f32), dcpos = at::empty({C, 3}, f32);
+  const int64_t nws = (int64_t)gs_camera_grad_workspace_bytes(P, (int32_t)C);
+  Tensor ws = at::empty({nws > 16 ? nws : 16}, f32.dtype(at::kByte));
+  check(gs_camera_grad_batch(&in.g, k.cams.data(), (int32_t)C, win.ptr, P ? radii_c.data_ptr<int32_t>() : nullptr,
+                             (int)compat, nz(geom), nz(scratch), ws.data_ptr(), (uint64_t)ws.numel(),
+                             dview.data_ptr<float>(), dproj.data_ptr<float>(), dcpos.data_ptr<float>(),
+                             reinterpret_cast<gs_stream_t>(stream)),
+        "camera_grad_batch");
+  return {dview, dproj, dcpos};
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -407,4 +443,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("abi_version", []() { return gs_version(); });
   m.def("forward_batch", &forward_batch);
   m.def("backward_batch", &backward_batch);
+  m.def("camera_grad_batch", &camera_grad_batch);
 }

@@ -8,6 +8,7 @@ What the reference computes in PyTorch and where:
     compute_psnr(pred, gt, mask)          metrics.py:14-43    -> psnr_clamped(image_metrics(pred, gt, mask))
     mPSNR().update(...) / .compute()      metrics.py:82-129   -> MaskedPSNR
     mSSIM().update(...) / .compute()      metrics.py:334-424  -> MaskedSSIM (image_metrics(...).ssim)
+    compute_pose_errors(preds, targets)   metrics.py:46-79    -> pose_errors (host numpy fp64, like the reference)
     mask_iou(a, b)                        metrics.py:222-250  -> iou(a, b)  (threshold 0.9)
     mIOU().update(...) / .compute()       metrics.py:295-331  -> MeanIoU
     MaskIoU().update(...) / .compute()    metrics.py:523-552  -> MaskIoU    (threshold 0)
@@ -33,8 +34,8 @@ documented defaults of torchmetrics' StructuralSimilarityIndexMeasure, which
 the reference inherits them from.
 
 Out of scope: LPIPS (mLPIPS needs network weights that do not ship with this
-package), PCK and compute_pose_errors (no 2-D tracks or camera poses are
-produced here), mMDE / unproject_image (file-writing, Open3D).
+package), PCK (no 2-D tracks are produced here), mMDE / unproject_image
+(file-writing, Open3D).
 """
 from __future__ import annotations
 
@@ -264,6 +265,39 @@ def iou(pred_mask: torch.Tensor, target_mask: torch.Tensor, threshold: float = 0
         counts: Callable = mask_iou) -> torch.Tensor:
     """The reference's mask_iou value per image: intersection over union, 1 for two empty masks."""
     return iou_ratio(*counts(pred_mask, target_mask, threshold))
+
+
+def pose_errors(preds, targets) -> Tuple[float, float, float]:
+    """The reference's compute_pose_errors (metrics.py:46-79) for two sequences
+    of N >= 2 camera-to-world poses ([N, 4, 4] tensors or arrays, e.g.
+    camera.PoseRefiner.poses() against the true poses): (ate, rpe_t,
+    rpe_r_deg) -- the mean distance of the camera centres; and, over the N - 1
+    consecutive pairs, with rel_i = pose_i^-1 pose_{i+1} and the error
+    target_rel_i^-1 pred_rel_i, the mean norm of its translation and the mean
+    angle of its rotation in degrees.  Host numpy in fp64 throughout: the
+    reference insists on numpy for the arccos near 1, where small angles live
+    (a reporting function of tiny inputs; it reads device tensors back)."""
+    import numpy as np
+
+    def host(x):
+        if isinstance(x, torch.Tensor):
+            x = x.detach().cpu().numpy()
+        x = np.asarray(x, dtype=np.float64)
+        if x.ndim != 3 or x.shape[1:] != (4, 4):
+            raise ValueError(f"poses must be [N, 4, 4], got {x.shape}")
+        return x
+
+    p, t = host(preds), host(targets)
+    if p.shape != t.shape or p.shape[0] < 2:
+        raise ValueError(f"preds and targets must be the same N >= 2 poses, got {p.shape} and {t.shape}")
+    ate = float(np.linalg.norm(p[:, :3, 3] - t[:, :3, 3], axis=-1).mean())
+    rel_p = np.linalg.inv(p[:-1]) @ p[1:]
+    rel_t = np.linalg.inv(t[:-1]) @ t[1:]
+    err = np.linalg.inv(rel_t) @ rel_p
+    rpe_t = float(np.linalg.norm(err[:, :3, 3], axis=-1).mean())
+    cos = np.clip((np.trace(err[:, :3, :3], axis1=-2, axis2=-1) - 1.0) / 2.0, -1.0, 1.0)
+    rpe_r = float(np.arccos(cos).mean()) / np.pi * 180.0
+    return ate, rpe_t, rpe_r
 
 
 # ---- accumulators: device tensors in update(), the only readback in compute()

@@ -441,20 +441,59 @@ class _BatchCameras:
         self.windows = wins if any(w is not None for w in wins) else None
 
 
+def _camera_tensor(t, C, tail, name):
+    """A per-call camera tensor (viewmatrices / projmatrices / campos) as the
+    binding takes it, (C, prod(tail)) fp32 contiguous and detached, or None."""
+    if t is None:
+        return None
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a tensor, got {type(t).__name__}")
+    n = 1
+    for d in tail:
+        n *= d
+    if tuple(t.shape) not in ((C, *tail), (C, n)):
+        raise ValueError(f"{name} must have shape {(C, *tail)} or {(C, n)} for {C} cameras, got {tuple(t.shape)}")
+    if t.dtype != torch.float32:
+        raise ValueError(f"{name} must be fp32, got {t.dtype}")
+    if not t.is_cuda:
+        raise ValueError(f"{name} must be a device tensor (it is on {t.device})")
+    return t.detach().reshape(C, n).contiguous()
+
+
 class _RasterizeGaussiansBatch(torch.autograd.Function):
     """_RasterizeGaussians over a list of camera settings (one launch per
-    stage for all of them); outputs stacked [C, ...]."""
+    stage for all of them); outputs stacked [C, ...].  `viewmatrices`,
+    `projmatrices`, `campos` (tensors, optional) replace the settings' stacked
+    camera tensors for the call and are differentiable (compat="fixed";
+    include/gs_camera_grad.h)."""
+
+    _CAMERA_SLOTS = (18, 19, 20)  # viewmatrices, projmatrices, campos in forward's arguments
 
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, semantic_feature, opacities, scales, rotations,
                 cov3Ds_precomp, cams, label, densify_out, raw_params=False, feature_ready=None, plan_state=None,
-                grad_into=None, walk_order=None, camera_frames=None):
+                grad_into=None, walk_order=None, camera_frames=None, viewmatrices=None, projmatrices=None,
+                campos=None):
         if not isinstance(cams, _BatchCameras):
             cams = _BatchCameras(cams)
         rs0 = cams.rs0
         compat = _compat_of(rs0)
         C = cams.C
         pp, views, projs, cpos = cams.pp, cams.views, cams.projs, cams.cpos
+        given = (viewmatrices, projmatrices, campos)
+        ctx.camera_grad = False
+        if any(t is not None for t in given):
+            ctx.camera_grad = any(ctx.needs_input_grad[i] for i in _RasterizeGaussiansBatch._CAMERA_SLOTS)
+            if ctx.camera_grad and compat != "fixed":
+                raise ValueError('camera gradients (viewmatrices / projmatrices / campos that require grad) need '
+                                 'compat="fixed": the reference-mode backward runs on swapped camera scalars (Q2) and '
+                                 'is not the derivative of its forward')
+            v_, p_, c_ = (_camera_tensor(t, C, tail, name) for t, tail, name in zip(
+                given, ((4, 4), (4, 4), (3,)), ("viewmatrices", "projmatrices", "campos")))
+            ctx.camera_shapes = tuple(None if t is None else tuple(t.shape) for t in given)
+            views = views if v_ is None else v_
+            projs = projs if p_ is None else p_
+            cpos = cpos if c_ is None else c_
         sh, colors_precomp, scales, rotations, cov3Ds_precomp = map(
             _empty_like_none, (sh, colors_precomp, scales, rotations, cov3Ds_precomp))
         tx, ty = cams.tx, cams.ty
@@ -504,6 +543,9 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
         # Q2 in reference mode, per camera (see _RasterizeGaussians.backward)
         cam4 = (tx, ty, cx, cy) if ctx.compat == "reference" else (cx, cy, tx, ty)
         fuse = _fusable(label, means3D)
+        if ctx.camera_grad and ctx.scratch is None and means3D.size(0) > 0:
+            # the camera kernel reads the accumulation records this backward leaves in its scratch
+            ctx.scratch = _C.batch_backward_scratch(means3D, semantic_feature, ctx.C)
         grads = _C.rasterize_gaussians_batch_backward(
             rs0.bg, means3D, radii, colors_precomp, semantic_feature, scales, rotations, rs0.scale_modifier,
             cov3Ds_precomp, views, projs, *cam4, grad_color, grad_out_feature, grad_depth, grad_alpha, sh,
@@ -515,7 +557,16 @@ class _RasterizeGaussiansBatch(torch.autograd.Function):
         if label is not None and not fuse and ctx.raw_params:
             raise RuntimeError("raw_params=True needs a per-Gaussian fp32 label (or none): the mask is "
                                "applied in-kernel before the activations' backward")
-        grads = _input_grads(grads, ctx.sem_shape, label, fuse) + (None,) * 9
+        cam_grads = (None, None, None)
+        if ctx.camera_grad:
+            # same stream, same state: the records are still in the scratch (compat is "fixed" here)
+            cam_grads = _C.rasterize_gaussians_batch_camera_grad(
+                rs0.bg, means3D, radii, cov3Ds_precomp, views, projs, cx, cy, tx, ty, rs0.image_height,
+                rs0.image_width, sh, rs0.sh_degree, cpos, geom, ctx.scratch, compat=ctx.compat, windows=windows,
+                cam_frames=ctx.camera_frames)
+            cam_grads = tuple(None if shape is None else g.view(shape)
+                              for g, shape in zip(cam_grads, ctx.camera_shapes))
+        grads = _input_grads(grads, ctx.sem_shape, label, fuse) + (None,) * 9 + cam_grads
         # gradients written into caller-owned destinations: autograd gets None
         taken = [False] * len(grads)
         for k in (ctx.grad_into or {}):
@@ -548,7 +599,7 @@ def _grad_destinations(grad_into, semantic_feature):
 def rasterize_gaussians_batch(means3D, means2D, sh, colors_precomp, semantic_feature, opacities, scales,
                               rotations, cov3Ds_precomp, settings_list, label=None, densify_out=None,
                               raw_params=False, feature_ready=None, plan_state=None, grad_into=None, walk_order=None,
-                              camera_frames=None):
+                              camera_frames=None, viewmatrices=None, projmatrices=None, campos=None):
     """rasterize_gaussians over a list of camera settings; outputs [C, ...]
     (color, radii, feature_map, depth, alpha).  `densify_out`: optional
     (accum, denom, max_radius) fp32 [P] tensors the backward fills with the
@@ -568,12 +619,16 @@ def rasterize_gaussians_batch(means3D, means2D, sh, colors_precomp, semantic_fea
     autograd paths are not added.  `walk_order`: the binning passes' walk
     order (_C.spatial_order; outputs do not depend on it).  `camera_frames`:
     a temporal window (GaussianRasterizerBatch; include/gs_window.h) -- C
-    non-decreasing frame indices; means3D is (P, B, 3) and its gradient too."""
+    non-decreasing frame indices; means3D is (P, B, 3) and its gradient too.
+    `viewmatrices` / `projmatrices` ((C, 4, 4) or (C, 16)) and `campos` ((C, 3)),
+    fp32 device tensors: replace the settings' camera tensors for this call
+    and receive gradients when they require grad (compat="fixed" only;
+    GaussianRasterizerBatch.forward)."""
     cams = settings_list if isinstance(settings_list, _BatchCameras) else _BatchCameras(list(settings_list))
     return _RasterizeGaussiansBatch.apply(means3D, means2D, sh, colors_precomp, semantic_feature, opacities,
                                           scales, rotations, cov3Ds_precomp, cams, label, densify_out,
                                           bool(raw_params), feature_ready, plan_state, grad_into, walk_order,
-                                          camera_frames)
+                                          camera_frames, viewmatrices, projmatrices, campos)
 
 
 def _check_frames(camera_frames, C):
@@ -601,8 +656,9 @@ class GaussianRasterizerBatch(nn.Module):
     densification statistics of the last backward in `densify_stats`
     (the reference's accumulate_mean2d_gradient / max_2D_radius inputs,
     external.py:136-140, train.py:288-290; see GradientSink).  The cameras'
-    matrices are stacked once at construction: build a new rasterizer when
-    they change (as the reference builds its settings per camera).
+    matrices are stacked once at construction; a call may replace them with
+    the `viewmatrices` / `projmatrices` / `campos` tensors of forward(), which
+    are differentiable (pose refinement).
 
     `raw_params=True` takes the Dynamic3DGaussians raw parameters as
     opacities / scales / rotations (logit_opacities, log_scales,
@@ -698,12 +754,31 @@ class GaussianRasterizerBatch(nn.Module):
 
     def forward(self, means3D, means2D, opacities=None, shs=None, semantic_feature=None, colors_precomp=None,
                 scales=None, rotations=None, cov3D_precomp=None, label=_UNSET, feature_ready=None,
-                grad_into=None):
+                grad_into=None, viewmatrices=None, projmatrices=None, campos=None):
         """The GaussianRasterizer call; `feature_ready` (keyword, optional): a
         recorded torch.cuda.Event the blend waits for before reading
         semantic_feature (gs_gaussians.feature_ready).  `grad_into` (keyword,
         optional): {argument name: tensor} destinations the backward writes
-        those gradients into (rasterize_gaussians_batch)."""
+        those gradients into (rasterize_gaussians_batch).
+
+        `viewmatrices`, `projmatrices` ((C, 4, 4) or (C, 16)) and `campos`
+        ((C, 3)) (keyword, optional; fp32 device tensors in the layout of
+        GaussianRasterizationSettings.viewmatrix / projmatrix / campos): when
+        given, each replaces the settings' stacked tensor for this call, so
+        poses that change every step need no new module (camera.PoseRefiner
+        produces all three).  When any of them requires grad, the backward
+        also launches the camera-gradient kernels (include/gs_camera_grad.h)
+        and returns their gradients in the given shapes: the exact derivative
+        of the compat="fixed" forward; compat="reference" then raises
+        ValueError here.  When none does, nothing extra is launched.  With a
+        `tile_window` the camera gradient is that of the window's pixels.  A
+        `label` masks per-Gaussian gradients only, not these.  Not
+        differentiated: tanfovx / tanfovy and c_x / c_y (the EWA focal lengths
+        are constants), so `projmatrices.grad` serves the chain view -> view @ P
+        of a pose, not the refinement of intrinsics.  Camera gradients are
+        not exchanged between ranks by distributed.ShardedStep and
+        TimestepDriver does not pass camera tensors.  A single camera is a
+        batch of one."""
         _check_inputs(shs, colors_precomp, scales, rotations, cov3D_precomp)
         if self.camera_frames is not None:
             if means3D.dim() != 3 or means3D.size(2) != 3 or means3D.size(1) <= self.camera_frames[-1]:
@@ -724,5 +799,5 @@ class GaussianRasterizerBatch(nn.Module):
         out = rasterize_gaussians_batch(
             means3D, means2D, shs, colors_precomp, semantic_feature, opacities, scales, rotations,
             cov3D_precomp, self._cams, lab, dens, self.raw_params, feature_ready, self.plan, grad_into,
-            self._walk_order(means3D), self.camera_frames)
+            self._walk_order(means3D), self.camera_frames, viewmatrices, projmatrices, campos)
         return _by_generation(has_label, semantic_feature is not None, *out)
