@@ -478,6 +478,48 @@ def rasterize_gaussians_batch_camera_grad(background, means3D, radii, cov3D_prec
         raise _lib.GsplatError(str(ex)) from None
 
 
+def rasterize_gaussians_batch_contributors(geomBuffer, binningBuffer, imgBuffer, num_instances, c_x, c_y, tan_fovx,
+                                           tan_fovy, background, viewmatrices, projmatrices, campos, image_height,
+                                           image_width, P, K, *, compat=None, windows=None):
+    """The K largest blend weights of every pixel and the Gaussians they
+    belong to (gs_contributors_batch, include/gs_track.h), to be called after
+    rasterize_gaussians_batch on the same stream with its state buffers, its
+    returned num_instances, its cameras and its tile `windows`.  Returns
+    (top_id int32 [C,K,H,W], top_w fp32 [C,K,H,W]): rank k holds the Gaussian
+    with the k-th largest w = alpha T among the entries the forward blended at
+    the pixel (the nearer one first between equal weights), -1 / 0 past the
+    number of blended entries and outside a camera's tile window.  K in 1..4.
+    P = 0 (the forward's empty buffers) gives -1 / 0 everywhere."""
+    cm = _compat_code(compat)
+    try:
+        return tuple(_native_mod().contributors_batch(
+            geomBuffer, _opt(binningBuffer), imgBuffer, [int(x) for x in num_instances], background, viewmatrices,
+            projmatrices, [float(x) for x in c_x], [float(x) for x in c_y], [float(x) for x in tan_fovx],
+            [float(x) for x in tan_fovy], int(image_height), int(image_width), campos, int(P), int(K), cm,
+            _windows_arg(windows), _lib.stream(viewmatrices.device)))
+    except RuntimeError as ex:
+        raise _lib.GsplatError(str(ex)) from None
+
+
+def track_project(means3D, ids, background, viewmatrices, projmatrices, c_x, c_y, tan_fovx, tan_fovy, campos,
+                  image_height, image_width):
+    """gs_track_project (include/gs_track.h): the means means3D[t, ids[n]]
+    ([T,P,3] fp32, ids [N] integer, device tensors) through each of the C
+    cameras as the forward's preprocess projects them.  Returns (uv [T,C,N,2],
+    depth [T,C,N], inside bool [T,C,N]); uv and depth equal the forward's
+    means2D and depths bit for bit, inside = in front of the camera and the
+    rounded pixel in the image; ids < 0 give zeros and inside = False."""
+    if means3D.device.type != "cuda":
+        raise _lib.GsplatError("the HIP track projection needs device tensors (means3D is on the CPU)")
+    try:
+        return tuple(_native_mod().track_project(
+            means3D, ids, background, viewmatrices, projmatrices, [float(x) for x in c_x], [float(x) for x in c_y],
+            [float(x) for x in tan_fovx], [float(x) for x in tan_fovy], int(image_height), int(image_width), campos,
+            _lib.stream(means3D.device)))
+    except RuntimeError as ex:
+        raise _lib.GsplatError(str(ex)) from None
+
+
 def _backward(background, means3D, radii, colors, semantic_feature, scales, rotations, scale_modifier,
               cov3D_precomp, viewmatrices, projmatrices, c_x, c_y, tan_fovx, tan_fovy, dL_dout_color,
               dL_dout_feature, dL_dout_depth, dL_dout_alpha, sh, degree, campos, geomBuffer, num_instances,

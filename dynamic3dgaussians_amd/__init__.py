@@ -19,7 +19,8 @@ Layout:
   scene_loss.py   the reference's floor / bg / soft_col_cons terms and its foreground split, no host syncs
                   (include/gs_scene_loss.h)
   metrics.py      the reference's quality reports: masked PSNR, masked SSIM, mask IoU (include/gs_metrics.h),
-                  pose errors
+                  pose errors, PCK
+  tracking.py     point tracking: top-K contributor maps, track projection, visibility (include/gs_track.h)
   motion.py       the reference's motion-basis warp: SE(3) basis blend, fused (include/gs_motion.h)
 """
 from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, GradientSink,  # noqa: F401
@@ -34,9 +35,11 @@ from .feature_loss import distillation_image_loss, feature_distillation_loss  # 
 from .densify import densify, densify_torch  # noqa: F401
 from .scene_loss import (foreground_split, gather_foreground, reference_extra_loss, regularizer_losses,  # noqa: F401
                          regularizer_losses_torch)
-from .metrics import (ImageMetrics, MaskedPSNR, MaskedSSIM, MaskIoU, MeanIoU, evaluate_cameras,  # noqa: F401
+from .metrics import (PCK, ImageMetrics, MaskedPSNR, MaskedSSIM, MaskIoU, MeanIoU, evaluate_cameras,  # noqa: F401
                       evaluate_sequence, image_metrics, image_metrics_torch, iou, mask_iou, mask_iou_torch,
                       pose_errors, psnr_clamped, psnr_masked, psnr_plain)
+from .tracking import (Tracks, contributor_maps, project_tracks, project_tracks_torch, select_gaussians,  # noqa: F401
+                       track_points, visible_in_maps)
 from .camera import PoseRefiner  # noqa: F401
 from .motion import (MotionBases, cont_6d_to_rmat, motion_positions, motion_positions_torch,  # noqa: F401
                      motion_transforms)

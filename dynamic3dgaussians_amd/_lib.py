@@ -164,6 +164,7 @@ class GsBatchHint(ctypes.Structure):
 
 GS_WINDOW_MAX_FRAMES = 64  # include/gs_window.h
 GS_CAMERA_GRAD_MAX_CAMS = 64  # include/gs_camera_grad.h
+GS_TRACK_MAX_K, GS_TRACK_MAX_CAMS = 4, 64  # include/gs_track.h
 
 
 class GsWindow(ctypes.Structure):
@@ -234,6 +235,14 @@ PROTOTYPES = {
                                             c_void_p, c_void_p]),
     "gs_camera_grad_batch": (ctypes.c_int, [P_G, P_C, c_int32, P_W, c_void_p, ctypes.c_int, c_void_p, c_void_p,
                                             c_void_p, ctypes.c_uint64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # include/gs_track.h
+    "gs_check_contributors": (ctypes.c_int, [c_int64, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "gs_contributors_batch": (ctypes.c_int, [P_C, c_int32, c_int64, ctypes.c_int, c_void_p, c_void_p, c_void_p,
+                                             ctypes.POINTER(c_int64), c_int32, c_void_p, c_void_p, c_void_p]),
+    "gs_check_track_project": (ctypes.c_int, [c_int64, c_int32, c_int32, c_int64, c_void_p, c_void_p, c_void_p,
+                                              c_void_p]),
+    "gs_track_project": (ctypes.c_int, [P_C, c_int32, c_int64, c_int32, c_void_p, c_void_p, c_int64, c_void_p,
+                                        c_void_p, c_void_p, c_void_p]),
     "gs_mark_visible": (ctypes.c_int, [c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gs_debug_export": (ctypes.c_int, [c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
                                        c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

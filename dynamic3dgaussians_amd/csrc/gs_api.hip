@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/gs_camera_grad.h"
+#include "../../include/gs_track.h"
 #include "../../include/gs_window.h"
 #include "../../include/gsplat_hip.h"
 #include "gs_common.h"
@@ -975,6 +976,57 @@ int gs_camera_grad_batch(const gs_gaussians* g, const gs_camera* cams, int32_t C
   }
   launch_camera_grad(a, cb, s);
   return launch_status("camera grad", 0, s);
+}
+
+// ---- point tracking (include/gs_track.h): the forward's walk repeated on the
+// state it left (the order table, the lists, the render records), and the
+// preprocess projection of chosen Gaussians over timesteps
+static_assert(GS_TRACK_MAX_CAMS == GS_MAX_CAMS, "gs_track.h and CamBatch");
+int gs_contributors_batch(const gs_camera* cams, int32_t C, int64_t P, int compat, const void* geom,
+                          const void* binning, const void* image, const int64_t* L, int32_t K, int32_t* top_id,
+                          float* top_w, gs_stream_t stream) {
+  if (!cams) return fail(-1, "null argument block");
+  if (compat != COMPAT_REFERENCE && compat != COMPAT_FIXED) return fail(-1, "contributors: unknown compat %d", compat);
+  const int W = cams[0].image_width, H = cams[0].image_height;
+  if (int e = gs_check_contributors(P, C, W, H, K, top_id, top_w)) return e;
+  hipStream_t s = (hipStream_t)stream;
+  ContribArgs a{};
+  a.W = W; a.H = H; a.grid_x = (W + TILE - 1) / TILE; a.num_tiles = a.grid_x * ((H + TILE - 1) / TILE); a.K = K;
+  a.top_id = top_id; a.top_w = top_w;
+  CamBatch cb{};
+  cb.C = C;
+  int64_t total = 0;
+  if (P > 0 && L)
+    for (int c = 0; c < C; ++c) total += L[c] > 0 ? L[c] : 0;
+  const bool walk = P > 0 && total > 0 && a.num_tiles > 0;
+  if (walk) {
+    if (!geom || !binning || !image) return fail(-1, "contributors: state buffers are required");
+    if (int e = make_batch(cams, C, (int)P, W, H, cb)) return e;
+    batch_bin_offsets(C, L, &cb);
+    a.order = at<uint4>(image, ImgLayout(W, H).order);
+    a.point_list = static_cast<const uint32_t*>(binning);
+    a.rec = at<float>(geom, GeomLayout(P).rec);
+  }
+  launch_contributors(a, cb, walk, s);
+  return launch_status("contributors", 0, s);
+}
+
+int gs_track_project(const gs_camera* cams, int32_t C, int64_t P, int32_t T, const float* means3D, const int32_t* ids,
+                     int64_t N, float* uv, float* depth, uint8_t* inside, gs_stream_t stream) {
+  if (!cams) return fail(-1, "null argument block");
+  if (int e = gs_check_track_project(P, T, C, N, ids, uv, depth, inside)) return e;
+  if ((int64_t)T * C * N == 0) return 0;
+  const int W = cams[0].image_width, H = cams[0].image_height;
+  if (W <= 0 || H <= 0) return fail(-1, "image size must be positive (got %dx%d)", W, H);
+  if (P > 0 && (!means3D || !cams[0].viewmatrix || !cams[0].projmatrix))
+    return fail(-1, "track project: means3D and the camera matrices are required");
+  CamBatch cb;
+  if (int e = make_batch(cams, C, (int)P, W, H, cb)) return e;
+  TrackProjectArgs a{};
+  a.P = (int)P; a.T = T; a.W = W; a.H = H; a.N = N;
+  a.means3D = means3D; a.ids = ids; a.uv = uv; a.depth = depth; a.inside = inside;
+  launch_track_project(a, cb, (hipStream_t)stream);
+  return launch_status("track project", 0, (hipStream_t)stream);
 }
 
 int gs_mark_visible(int64_t P, const float* means3D, const float* viewmatrix, const float* projmatrix,

@@ -168,6 +168,29 @@ struct CameraGradArgs {
 // P = 0: only the finishing kernel runs (zeros); cb is then read for C alone
 void launch_camera_grad(const CameraGradArgs& a, const CamBatch& cb, hipStream_t s);
 
+// Point tracking (gs_track.hip, include/gs_track.h).
+// The forward's walk repeated for the K largest blend weights of every pixel.
+struct ContribArgs {
+  int W, H, grid_x, num_tiles, K;
+  const uint4* order;          // camera 0's dispatch records; per camera at img_stride
+  const uint32_t* point_list;  // the batch's binning base; camera c's list at CamBatch::bin_off[c]
+  const float* rec;            // camera 0's P x REC render records; per camera at geom_stride
+  int32_t* top_id;             // C x K x H x W
+  float* top_w;                // C x K x H x W
+};
+// walk = false (P = 0 or no instance): every element -1 / 0, no state buffer is read
+void launch_contributors(const ContribArgs& a, const CamBatch& cb, bool walk, hipStream_t s);
+struct TrackProjectArgs {
+  int P, T, W, H;
+  int64_t N;
+  const float* means3D;  // T x P x 3
+  const int32_t* ids;    // N
+  float* uv;             // T x C x N x 2
+  float* depth;          // T x C x N
+  uint8_t* inside;       // T x C x N
+};
+void launch_track_project(const TrackProjectArgs& a, const CamBatch& cb, hipStream_t s);
+
 // Stable LSD radix sort on bits [0, end_bit) (the standalone gs_sort_pairs
 // entry point); the result ends in keys0/vals0 or keys1/vals1 -- returns 0
 // or 1 for which (passes of 8 bits swap slots).

@@ -13,14 +13,9 @@
 #include "gs_activate.h"
 #include "gs_common.h"
 #include "gs_kernels.h"
-#include "gs_project.h"  // SH constants, V3, xf43 / xf44, ewa_setup / ewa_cov2d
+#include "gs_project.h"  // SH constants, V3, xf43 / xf44, ndc_to_pix, ewa_setup / ewa_cov2d
 
 namespace gs {
-
-// ndc2Pix in double (double literals at auxiliary.h:43).
-__device__ inline float ndc_to_pix(float v, int S) {
-  return (float)((((double)v + 1.0) * (double)S - 1.0) * 0.5);
-}
 
 // getRect (auxiliary.h:46-56).
 __device__ inline void tile_rect(float px, float py, int r, int gx, int gy, int2& rmin, int2& rmax) {

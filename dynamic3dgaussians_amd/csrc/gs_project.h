@@ -1,8 +1,9 @@
 // gs_project.h -- the projection pieces shared by the preprocess kernels
-// (gs_preprocess.hip) and the camera-gradient kernel (gs_camera_grad.hip):
-// point transforms, the EWA setup of computeCov2D and the SH constants.  Both
-// files are compiled with -ffp-contract=off, so every expression keeps the
-// operation order of the CPU oracle (oracle/gs_oracle.c).
+// (gs_preprocess.hip), the camera-gradient kernel (gs_camera_grad.hip) and the
+// track projection (gs_track.hip): point transforms, the pixel convention, the
+// EWA setup of computeCov2D and the SH constants.  These files are compiled
+// with -ffp-contract=off, so every expression keeps the operation order of the
+// CPU oracle (oracle/gs_oracle.c).
 #pragma once
 
 #include "gs_common.h"
@@ -34,6 +35,11 @@ __device__ inline float4 xf44(const float* __restrict__ m, V3 p) {
                      m[1] * p.x + m[5] * p.y + m[9] * p.z + m[13],
                      m[2] * p.x + m[6] * p.y + m[10] * p.z + m[14],
                      m[3] * p.x + m[7] * p.y + m[11] * p.z + m[15]);
+}
+
+// ndc2Pix in double (double literals at auxiliary.h:43).
+__device__ inline float ndc_to_pix(float v, int S) {
+  return (float)((((double)v + 1.0) * (double)S - 1.0) * 0.5);
 }
 
 // Shared EWA setup (forward.cu:75-118 / backward.cu:166-211).

@@ -18,6 +18,7 @@
 #include <tuple>
 
 #include "gs_camera_grad.h"
+#include "gs_track.h"
 #include "gs_window.h"
 #include "gsplat_hip.h"
 
@@ -436,6 +437,67 @@ std::tuple<Tensor, Tensor, Tensor> camera_grad_batch(
   return {dview, dproj, dcpos};
 }
 
+// The K largest blend weights of every pixel and their Gaussians
+// (gs_track.h), after forward_batch on the same stream from the state buffers
+// that call returned: (top_id int32 [C,K,H,W], top_w [C,K,H,W]).
+std::tuple<Tensor, Tensor> contributors_batch(
+    const Tensor& geom, const OptT& binning, const Tensor& img, const std::vector<int64_t>& num_instances,
+    const Tensor& bg, const Tensor& views, const Tensor& projs, const std::vector<double>& cx,
+    const std::vector<double>& cy, const std::vector<double>& tx, const std::vector<double>& ty, int64_t H, int64_t W,
+    const Tensor& campos, int64_t P, int64_t K, int64_t compat, const std::vector<std::vector<int64_t>>& windows,
+    int64_t stream) {
+  const at::Device dev = views.device();
+  Cameras k(dev, bg, views, projs, campos, cx, cy, tx, ty, W, H, windows);
+  const int64_t C = (int64_t)k.cams.size();
+  if ((int64_t)num_instances.size() != C) throw std::runtime_error("num_instances must have C entries");
+  if (K < 1 || K > GS_TRACK_MAX_K)
+    throw std::runtime_error("K = " + std::to_string(K) + " outside 1.." + std::to_string(GS_TRACK_MAX_K));
+  const Tensor bin = binning.has_value() ? *binning : Tensor();
+  if (P > 0) {
+    if (geom.device() != dev || img.device() != dev || (bin.defined() && bin.numel() && bin.device() != dev))
+      throw std::runtime_error("contributors_batch: the state buffers must be on the cameras' device");
+    if (geom.numel() < (int64_t)gs_batch_geom_buffer_bytes(P, (int32_t)C) ||
+        img.numel() < (int64_t)gs_batch_image_buffer_bytes((int32_t)W, (int32_t)H, (int32_t)C) ||
+        (bin.defined() ? bin.numel() : 0) < (int64_t)gs_batch_binning_buffer_bytes((int32_t)C, num_instances.data()))
+      throw std::runtime_error("contributors_batch: geom, binning and img must be the forward's buffers for P, the "
+                               "image size and num_instances");
+  }
+  const auto opt = at::TensorOptions().device(dev);
+  Tensor top_id = at::empty({C, K, H, W}, opt.dtype(at::kInt));
+  Tensor top_w = at::empty({C, K, H, W}, opt.dtype(at::kFloat));
+  check(gs_contributors_batch(k.cams.data(), (int32_t)C, P, (int)compat, nz(geom), nz(bin), nz(img),
+                              num_instances.data(), (int32_t)K, static_cast<int32_t*>(nz(top_id)),
+                              static_cast<float*>(nz(top_w)), reinterpret_cast<gs_stream_t>(stream)),
+        "contributors_batch");
+  return {top_id, top_w};
+}
+
+// means3D [T,P,3] and ids [N] through the C cameras (gs_track.h):
+// (uv [T,C,N,2], depth [T,C,N], inside bool [T,C,N]).
+std::tuple<Tensor, Tensor, Tensor> track_project(
+    const Tensor& means3D, const Tensor& ids, const Tensor& bg, const Tensor& views, const Tensor& projs,
+    const std::vector<double>& cx, const std::vector<double>& cy, const std::vector<double>& tx,
+    const std::vector<double>& ty, int64_t H, int64_t W, const Tensor& campos, int64_t stream) {
+  if (means3D.dim() != 3 || means3D.size(2) != 3)
+    throw std::runtime_error("means3D must have dimensions (timesteps, num_points, 3)");
+  const at::Device dev = means3D.device();
+  Tensor m = dev_f32(means3D, dev, "means3D");
+  if (ids.device() != dev || ids.dim() != 1) throw std::runtime_error("ids must be a 1-D tensor on means3D's device");
+  Tensor id32 = ids.to(at::kInt).contiguous();
+  Cameras k(dev, bg, views, projs, campos, cx, cy, tx, ty, W, H, {});
+  const int64_t C = (int64_t)k.cams.size(), T = m.size(0), P = m.size(1), N = id32.size(0);
+  const auto opt = at::TensorOptions().device(dev);
+  Tensor uv = at::empty({T, C, N, 2}, opt.dtype(at::kFloat));
+  Tensor depth = at::empty({T, C, N}, opt.dtype(at::kFloat));
+  Tensor inside = at::empty({T, C, N}, opt.dtype(at::kBool));
+  check(gs_track_project(k.cams.data(), (int32_t)C, P, (int32_t)T, static_cast<const float*>(nz(m)),
+                         static_cast<const int32_t*>(nz(id32)), N, static_cast<float*>(nz(uv)),
+                         static_cast<float*>(nz(depth)), static_cast<uint8_t*>(nz(inside)),
+                         reinterpret_cast<gs_stream_t>(stream)),
+        "track_project");
+  return {uv, depth, inside};
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -444,4 +506,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("forward_batch", &forward_batch);
   m.def("backward_batch", &backward_batch);
   m.def("camera_grad_batch", &camera_grad_batch);
+  m.def("contributors_batch", &contributors_batch);
+  m.def("track_project", &track_project);
 }

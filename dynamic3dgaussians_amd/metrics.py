@@ -33,9 +33,11 @@ are clamped.  Its constants (window 11, sigma 1.5, k1 0.01, k2 0.03) are the
 documented defaults of torchmetrics' StructuralSimilarityIndexMeasure, which
 the reference inherits them from.
 
+    PCK().update(...) / .compute()        metrics.py:489-520  -> PCK        (plain torch; the 2-D tracks
+                                                                             come from tracking.track_points)
+
 Out of scope: LPIPS (mLPIPS needs network weights that do not ship with this
-package), PCK (no 2-D tracks are produced here), mMDE / unproject_image
-(file-writing, Open3D).
+package), mMDE / unproject_image (file-writing, Open3D).
 """
 from __future__ import annotations
 
@@ -391,6 +393,42 @@ class MeanIoU(_Accumulator):
 
     def result(self) -> torch.Tensor:
         return torch.cat(self._entries).mean()
+
+
+class PCK(_Accumulator):
+    """The reference's PCK (metrics.py:489-520), the share of correct keypoints: every update
+    is one entry, the count of predictions preds [N, 2] strictly nearer than `threshold` (in
+    pixels) to their targets [N, 2] and N; compute() is the mean over the entries of
+    correct / max(total, 1e-8) -- a mean of per-update ratios, and 0 for an empty update: the
+    reference's final line, kept.  `visible` ([N] bool, optional; no reference analogue, its
+    callers index the visible points first): the update counts the visible targets only, as
+    preds[visible] / targets[visible] would, without the host synchronisation of a boolean
+    index.  Plain torch on the tensors' device (tracking.track_points produces the
+    predictions); nothing is read back before compute()."""
+
+    def __init__(self):
+        self._entries = []  # (correct, total) pairs, each [1] fp64
+
+    def update(self, preds: torch.Tensor, targets: torch.Tensor, threshold: float,
+               visible: Optional[torch.Tensor] = None) -> None:
+        if preds.shape != targets.shape or preds.dim() != 2:
+            raise GsplatError(f"preds and targets must both be [N, D] (got {tuple(preds.shape)} and "
+                              f"{tuple(targets.shape)})")
+        ok = torch.linalg.norm(preds - targets, dim=-1) < threshold
+        if visible is None:
+            total = torch.full((1,), float(preds.shape[0]), dtype=torch.float64, device=preds.device)
+        else:
+            if visible.shape != ok.shape:
+                raise GsplatError(f"visible must have shape {tuple(ok.shape)} (got {tuple(visible.shape)})")
+            vis = visible.to(device=ok.device, dtype=torch.bool)
+            ok = ok & vis
+            total = vis.sum().double().reshape(1)
+        self._entries.append((ok.sum().double().reshape(1), total))
+
+    def result(self) -> torch.Tensor:
+        correct = torch.cat([e[0] for e in self._entries])
+        total = torch.cat([e[1] for e in self._entries])
+        return (correct / total.clamp(min=1e-8)).mean()
 
 
 # ---- a forward-only batch render, scored

@@ -34,7 +34,7 @@ _SORT_COPY = ("gs_tiles.hip",
               "  if (n <= cap) {\n    // keys straight from global memory")
 
 # strip_of_block: the XCD rotation at every camera count (C >= 8 too)
-_ROT_ALL = ("gs_render.hip",
+_ROT_ALL = ("gs_blend.h",
             "    u = k * 8 + ((x + (C < CAM_GROUP ? k : 0)) & 7);\n",
             "    u = k * 8 + ((x + k) & 7);\n")
 
