@@ -19,7 +19,9 @@ Layout:
   scene_loss.py   the reference's floor / bg / soft_col_cons terms and its foreground split, no host syncs
                   (include/gs_scene_loss.h)
   metrics.py      the reference's quality reports: masked PSNR, masked SSIM, mask IoU (include/gs_metrics.h),
-                  pose errors, PCK
+                  pose errors, PCK, the mMDE depth error
+  depth_geometry.py  geometry on depth maps: point z-buffer and abs-rel score, unprojection, depth-induced flow,
+                  bilinear border sampling, flow warping and chaining, track lifting (include/gs_depth_geometry.h)
   tracking.py     point tracking: top-K contributor maps, track projection, visibility (include/gs_track.h)
   motion.py       the reference's motion-basis warp: SE(3) basis blend, fused (include/gs_motion.h)
 """
@@ -35,9 +37,14 @@ from .feature_loss import distillation_image_loss, feature_distillation_loss  # 
 from .densify import densify, densify_torch  # noqa: F401
 from .scene_loss import (foreground_split, gather_foreground, reference_extra_loss, regularizer_losses,  # noqa: F401
                          regularizer_losses_torch)
-from .metrics import (PCK, ImageMetrics, MaskedPSNR, MaskedSSIM, MaskIoU, MeanIoU, evaluate_cameras,  # noqa: F401
-                      evaluate_sequence, image_metrics, image_metrics_torch, iou, mask_iou, mask_iou_torch,
-                      pose_errors, psnr_clamped, psnr_masked, psnr_plain)
+from .metrics import (PCK, ImageMetrics, MaskedPSNR, MaskedSSIM, MaskIoU, MeanDepthError, MeanIoU,  # noqa: F401
+                      evaluate_cameras, evaluate_sequence, image_metrics, image_metrics_torch, iou, mask_iou,
+                      mask_iou_torch, pose_errors, psnr_clamped, psnr_masked, psnr_plain)
+from .depth_geometry import (accumulate_flows, accumulate_flows_torch, depth_abs_rel, depth_abs_rel_torch,  # noqa: F401
+                             depth_flow, depth_flow_torch, lift_tracks, lift_tracks_torch, point_depth_maps,
+                             point_depth_maps_torch, resize_flow, resize_flow_torch, sample_bilinear,
+                             sample_bilinear_torch, unproject_depth, unproject_depth_torch, warp_flow,
+                             warp_flow_torch)
 from .tracking import (Tracks, contributor_maps, project_tracks, project_tracks_torch, select_gaussians,  # noqa: F401
                        track_points, visible_in_maps)
 from .camera import PoseRefiner  # noqa: F401

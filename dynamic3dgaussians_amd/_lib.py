@@ -96,6 +96,42 @@ class GsImageMetrics(ctypes.Structure):
                 ("_pad", c_int32), ("out", c_void_p), ("workspace", c_void_p), ("workspace_bytes", ctypes.c_uint64)]
 
 
+GS_SAMPLE_POINTS, GS_SAMPLE_DISPLACEMENT = 0, 1  # include/gs_depth_geometry.h
+
+
+class GsPointDepth(ctypes.Structure):
+    """include/gs_depth_geometry.h struct gs_point_depth."""
+    _fields_ = [("P", c_int64), ("B", c_int32), ("H", c_int32), ("W", c_int32), ("_pad", c_int32),
+                ("points", c_void_p), ("points_batch_stride", c_int64), ("w2c", c_void_p), ("K", c_void_p),
+                ("depth", c_void_p)]
+
+
+class GsDepthAbsRel(ctypes.Structure):
+    """include/gs_depth_geometry.h struct gs_depth_abs_rel."""
+    _fields_ = [("B", c_int32), ("H", c_int32), ("W", c_int32), ("_pad", c_int32), ("est", c_void_p),
+                ("gt", c_void_p), ("exclude", c_void_p), ("exclude_batch_stride", c_int64), ("out", c_void_p),
+                ("workspace", c_void_p), ("workspace_bytes", ctypes.c_uint64)]
+
+
+class GsDepthUnproject(ctypes.Structure):
+    """include/gs_depth_geometry.h struct gs_depth_unproject."""
+    _fields_ = [("B", c_int32), ("H", c_int32), ("W", c_int32), ("_pad", c_int32), ("depth", c_void_p),
+                ("xy", c_void_p), ("Kinv", c_void_p), ("c2w", c_void_p), ("xyz", c_void_p)]
+
+
+class GsDepthFlow(ctypes.Structure):
+    """include/gs_depth_geometry.h struct gs_depth_flow."""
+    _fields_ = [("B", c_int32), ("H", c_int32), ("W", c_int32), ("_pad", c_int32), ("depth1", c_void_p),
+                ("Kinv1", c_void_p), ("T", c_void_p), ("K2", c_void_p), ("flow", c_void_p), ("valid", c_void_p)]
+
+
+class GsSampleBilinear(ctypes.Structure):
+    """include/gs_depth_geometry.h struct gs_sample_bilinear."""
+    _fields_ = [("B", c_int32), ("Ch", c_int32), ("H", c_int32), ("W", c_int32), ("mode", c_int32),
+                ("add_displacement", c_int32), ("N", c_int64), ("h", c_int32), ("w", c_int32), ("src", c_void_p),
+                ("coords", c_void_p), ("out", c_void_p)]
+
+
 GS_DENSIFY_MAX_TENSORS = 16  # include/gs_densify.h
 GS_DENSIFY_N_SPLIT = 2
 GS_DENSIFY_ROLES = {"plain": 0, "means": 1, "log_scales": 2, "rotations": 3, "logit_opacities": 4}
@@ -310,6 +346,23 @@ PROTOTYPES = {
     "gs_image_metrics": (ctypes.c_int, [ctypes.POINTER(GsImageMetrics), c_void_p]),
     "gs_mask_iou_validate": (ctypes.c_int, [c_int32, c_int64, c_void_p, c_void_p, c_float, c_void_p]),
     "gs_mask_iou": (ctypes.c_int, [c_int32, c_int64, c_void_p, c_void_p, c_float, c_void_p, c_void_p]),
+    # include/gs_depth_geometry.h
+    "gs_point_depth_struct_bytes": (c_size_t, []),
+    "gs_depth_abs_rel_struct_bytes": (c_size_t, []),
+    "gs_depth_unproject_struct_bytes": (c_size_t, []),
+    "gs_depth_flow_struct_bytes": (c_size_t, []),
+    "gs_sample_bilinear_struct_bytes": (c_size_t, []),
+    "gs_depth_abs_rel_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
+    "gs_point_depth_validate": (ctypes.c_int, [ctypes.POINTER(GsPointDepth)]),
+    "gs_depth_abs_rel_validate": (ctypes.c_int, [ctypes.POINTER(GsDepthAbsRel)]),
+    "gs_depth_unproject_validate": (ctypes.c_int, [ctypes.POINTER(GsDepthUnproject)]),
+    "gs_depth_flow_validate": (ctypes.c_int, [ctypes.POINTER(GsDepthFlow)]),
+    "gs_sample_bilinear_validate": (ctypes.c_int, [ctypes.POINTER(GsSampleBilinear)]),
+    "gs_point_depth": (ctypes.c_int, [ctypes.POINTER(GsPointDepth), c_void_p]),
+    "gs_depth_abs_rel": (ctypes.c_int, [ctypes.POINTER(GsDepthAbsRel), c_void_p]),
+    "gs_depth_unproject": (ctypes.c_int, [ctypes.POINTER(GsDepthUnproject), c_void_p]),
+    "gs_depth_flow": (ctypes.c_int, [ctypes.POINTER(GsDepthFlow), c_void_p]),
+    "gs_sample_bilinear": (ctypes.c_int, [ctypes.POINTER(GsSampleBilinear), c_void_p]),
     # include/gs_densify.h
     "gs_densify_plan_struct_bytes": (c_size_t, []),
     "gs_densify_tensor_struct_bytes": (c_size_t, []),

@@ -36,8 +36,13 @@ the reference inherits them from.
     PCK().update(...) / .compute()        metrics.py:489-520  -> PCK        (plain torch; the 2-D tracks
                                                                              come from tracking.track_points)
 
+    unproject_image(...) / mMDE()         metrics.py:131-213, 254-292 -> MeanDepthError (the z-buffer and the
+                                                                             abs-rel score are depth_geometry's
+                                                                             point_depth_maps / depth_abs_rel)
+
 Out of scope: LPIPS (mLPIPS needs network weights that do not ship with this
-package), mMDE / unproject_image (file-writing, Open3D).
+package) and the image file unproject_image saves of its estimated depth map
+(save_depth_map; point_depth_maps returns the map).
 """
 from __future__ import annotations
 
@@ -431,11 +436,40 @@ class PCK(_Accumulator):
         return (correct / total.clamp(min=1e-8)).mean()
 
 
+class MeanDepthError(_Accumulator):
+    """The reference's mMDE (metrics.py:254-292): the mean over images of unproject_image's
+    absolute relative depth error.  update(points, w2c, K, depth_gt, exclude) projects the
+    cloud points [P, 3] (or [B, P, 3], one per camera) into the cameras w2c [B, 4, 4],
+    K [B, 3, 3], keeps the nearest point per pixel and scores the map against depth_gt
+    [B, H, W] where it is finite, depth_gt > 0 and exclude != 1 (exclude [H, W] or [B, H, W],
+    optional): one entry per image, as a loop of the reference's per-image updates.  compute()
+    is the mean of the entries (NaN if an image had no valid pixel, as the reference's).
+    `maps` / `score`: depth_geometry's point_depth_maps / depth_abs_rel (HIP, device tensors)
+    or their _torch twins.  Nothing is read back before compute()."""
+
+    def __init__(self, maps: Optional[Callable] = None, score: Optional[Callable] = None):
+        from . import depth_geometry
+        self.maps = maps if maps is not None else depth_geometry.point_depth_maps
+        self.score = score if score is not None else depth_geometry.depth_abs_rel
+        self._entries = []  # [n] fp64 per update
+
+    def update(self, points, w2c, K, depth_gt, exclude=None) -> None:
+        est = self.maps(points, w2c, K, depth_gt.shape[-2:])
+        self.update_images(self.score(est, depth_gt, exclude))
+
+    def update_images(self, scores: torch.Tensor) -> None:
+        self._entries.append(scores.double().reshape(-1))
+
+    def result(self) -> torch.Tensor:
+        return torch.cat(self._entries).mean()
+
+
 # ---- a forward-only batch render, scored
 
 def evaluate_cameras(rendervar: dict, settings_all, targets: torch.Tensor, masks: Optional[torch.Tensor] = None, *,
                      seg: Optional[torch.Tensor] = None, seg_targets: Optional[torch.Tensor] = None,
-                     clip: bool = True) -> dict:
+                     clip: bool = True, depth_gt: Optional[torch.Tensor] = None,
+                     depth_exclude: Optional[torch.Tensor] = None) -> dict:
     """Render the cameras `settings_all` (a list of GaussianRasterizationSettings, or a
     GaussianRasterizerBatch built from one, reused over calls) from `rendervar`
     (timesteps.params2rendervar) in one forward-only batch launch and score the images against
@@ -447,7 +481,10 @@ def evaluate_cameras(rendervar: dict, settings_all, targets: torch.Tensor, masks
     Returns per-camera device tensors, nothing read back: image (the scored render), metrics
     (the ImageMetrics), sse, sae, mask_sum, ssim, l1, psnr (calc_psnr; over the masked pair
     when masks are given), psnr_masked (the mPSNR update, with masks), and intersection, union,
-    iou with seg.  Runs under torch.no_grad(): the parameters get no .grad."""
+    iou with seg.  With `depth_gt` [C, H, W] (and `depth_exclude`, [H, W] or [C, H, W],
+    optional) also mde: the mMDE score of the cloud rendervar["means3D"] in each camera of the
+    settings (depth_geometry.point_depth_maps and depth_abs_rel).  Runs under torch.no_grad():
+    the parameters get no .grad."""
     from .rasterizer import GaussianRasterizerBatch
     with torch.no_grad():
         ras = settings_all if isinstance(settings_all, GaussianRasterizerBatch) else \
@@ -470,6 +507,13 @@ def evaluate_cameras(rendervar: dict, settings_all, targets: torch.Tensor, masks
         if seg is not None:
             i, u = mask_iou(seg, seg_targets, 0.9)
             out.update(intersection=i, union=u, iou=iou_ratio(i, u))
+        if depth_gt is None and depth_exclude is not None:
+            raise GsplatError("depth_exclude comes with depth_gt")
+        if depth_gt is not None:
+            from . import depth_geometry as dg
+            w2c, K, hw = dg.cameras_of_settings(ras.settings_list)
+            est = dg.point_depth_maps(rv["means3D"].contiguous(), w2c, K, hw)
+            out["mde"] = dg.depth_abs_rel(est, depth_gt, depth_exclude)
         return out
 
 
