@@ -24,6 +24,8 @@ Layout:
                   bilinear border sampling, flow warping and chaining, track lifting (include/gs_depth_geometry.h)
   tracking.py     point tracking: top-K contributor maps, track projection, visibility (include/gs_track.h)
   motion.py       the reference's motion-basis warp: SE(3) basis blend, fused (include/gs_motion.h)
+  motion_init.py  the motion bases' initialisation: k-means, per-cluster medians, coefficients, one weighted
+                  Procrustes solve per (basis, frame) (include/gs_motion_init.h)
 """
 from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, GradientSink,  # noqa: F401
                          _RasterizeGaussians, rasterize_gaussians)
@@ -50,5 +52,10 @@ from .tracking import (Tracks, contributor_maps, project_tracks, project_tracks_
 from .camera import PoseRefiner  # noqa: F401
 from .motion import (MotionBases, cont_6d_to_rmat, motion_positions, motion_positions_torch,  # noqa: F401
                      motion_transforms)
+from .motion_init import (KMeansResult, MotionInit, ProcrustesInit, cluster_medians, cluster_medians_torch,  # noqa: F401
+                          coefs_from_centers, coefs_from_centers_torch, init_motion_bases_from_tracks,
+                          init_motion_coefs_from_features, kmeans, kmeans_assign, kmeans_assign_torch, kmeans_torch,
+                          kmeans_update, kmeans_update_torch, solve_procrustes_bases,
+                          solve_procrustes_bases_torch, velocity_directions)
 
 __version__ = "0.1.0"

@@ -132,6 +132,34 @@ class GsSampleBilinear(ctypes.Structure):
                 ("coords", c_void_p), ("out", c_void_p)]
 
 
+class GsKmeansAssign(ctypes.Structure):
+    """include/gs_motion_init.h struct gs_kmeans_assign."""
+    _fields_ = [("N", c_int64), ("D", c_int32), ("K", c_int32), ("x", c_void_p), ("centers", c_void_p),
+                ("valid", c_void_p), ("prev_labels", c_void_p), ("labels", c_void_p), ("moved", c_void_p)]
+
+
+class GsKmeansUpdate(ctypes.Structure):
+    """include/gs_motion_init.h struct gs_kmeans_update."""
+    _fields_ = [("N", c_int64), ("D", c_int32), ("K", c_int32), ("x", c_void_p), ("labels", c_void_p),
+                ("centers", c_void_p), ("counts", c_void_p), ("workspace", c_void_p),
+                ("workspace_bytes", ctypes.c_uint64)]
+
+
+class GsCoefsFromCenters(ctypes.Structure):
+    """include/gs_motion_init.h struct gs_coefs_from_centers."""
+    _fields_ = [("N", c_int64), ("K", c_int32), ("_pad", c_int32), ("means", c_void_p), ("centers", c_void_p),
+                ("coefs", c_void_p)]
+
+
+class GsProcrustes(ctypes.Structure):
+    """include/gs_motion_init.h struct gs_procrustes."""
+    _fields_ = [("N", c_int64), ("T", c_int32), ("K", c_int32), ("cano_t", c_int32), ("rot_dim", c_int32),
+                ("min_weight_sum", ctypes.c_double), ("tracks", c_void_p), ("order", c_void_p), ("offsets", c_void_p),
+                ("weights", c_void_p), ("confidences", c_void_p), ("rots", c_void_p), ("transls", c_void_p),
+                ("err_after", c_void_p), ("err_before", c_void_p), ("skipped", c_void_p), ("workspace", c_void_p),
+                ("workspace_bytes", ctypes.c_uint64)]
+
+
 GS_DENSIFY_MAX_TENSORS = 16  # include/gs_densify.h
 GS_DENSIFY_N_SPLIT = 2
 GS_DENSIFY_ROLES = {"plain": 0, "means": 1, "log_scales": 2, "rotations": 3, "logit_opacities": 4}
@@ -363,6 +391,21 @@ PROTOTYPES = {
     "gs_depth_unproject": (ctypes.c_int, [ctypes.POINTER(GsDepthUnproject), c_void_p]),
     "gs_depth_flow": (ctypes.c_int, [ctypes.POINTER(GsDepthFlow), c_void_p]),
     "gs_sample_bilinear": (ctypes.c_int, [ctypes.POINTER(GsSampleBilinear), c_void_p]),
+    # include/gs_motion_init.h
+    "gs_kmeans_assign_struct_bytes": (c_size_t, []),
+    "gs_kmeans_update_struct_bytes": (c_size_t, []),
+    "gs_coefs_from_centers_struct_bytes": (c_size_t, []),
+    "gs_procrustes_struct_bytes": (c_size_t, []),
+    "gs_kmeans_workspace_bytes": (c_size_t, [c_int64, c_int32, c_int32]),
+    "gs_procrustes_workspace_bytes": (c_size_t, [c_int32, c_int32]),
+    "gs_kmeans_assign_validate": (ctypes.c_int, [ctypes.POINTER(GsKmeansAssign)]),
+    "gs_kmeans_update_validate": (ctypes.c_int, [ctypes.POINTER(GsKmeansUpdate)]),
+    "gs_coefs_from_centers_validate": (ctypes.c_int, [ctypes.POINTER(GsCoefsFromCenters)]),
+    "gs_procrustes_validate": (ctypes.c_int, [ctypes.POINTER(GsProcrustes)]),
+    "gs_kmeans_assign": (ctypes.c_int, [ctypes.POINTER(GsKmeansAssign), c_void_p]),
+    "gs_kmeans_update": (ctypes.c_int, [ctypes.POINTER(GsKmeansUpdate), c_void_p]),
+    "gs_coefs_from_centers": (ctypes.c_int, [ctypes.POINTER(GsCoefsFromCenters), c_void_p]),
+    "gs_procrustes": (ctypes.c_int, [ctypes.POINTER(GsProcrustes), c_void_p]),
     # include/gs_densify.h
     "gs_densify_plan_struct_bytes": (c_size_t, []),
     "gs_densify_tensor_struct_bytes": (c_size_t, []),

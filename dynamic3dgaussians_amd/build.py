@@ -74,6 +74,7 @@ SOURCES = {
     "gs_camera_grad.hip": ["-ffp-contract=off"],  # the per-pair terms in preprocess_bwd's operation order
     "gs_track.hip": ["-ffp-contract=off"],  # the projection in preprocess_fwd's operation order
     "gs_depth_geometry.hip": ["-ffp-contract=off"],  # products and sums round as written, as the torch restatement's
+    "gs_motion_init.hip": ["-ffp-contract=off"],  # squared differences round as written, as the torch restatement's
     "gs_api.hip": [],
     "gs_host.cpp": [],  # host-only C++ (also built by oracle/Makefile's sanitizer target)
     "gs_densify_host.cpp": [],  # host-only C++ (also built into tools/densify_host_sanitize.c's program)
@@ -88,6 +89,8 @@ SOURCES = {
     "gs_track_host.cpp": [],  # host-only C++ (also built into tools/track_host_sanitize.c's program)
     # host-only C++ (also built into tools/depth_geometry_host_sanitize.c's program)
     "gs_depth_geometry_host.cpp": [],
+    # host-only C++ (also built into tools/motion_init_host_sanitize.c's program)
+    "gs_motion_init_host.cpp": [],
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall",
           "-Wno-unused-function", "-I", CSRC, "-I", INCLUDE]
