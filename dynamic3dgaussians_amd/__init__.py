@@ -13,6 +13,8 @@ Layout:
   distributed.py  camera-sharded data parallelism with one RCCL all-reduce
   image_loss.py   the reference's L1 + SSIM photometric loss, fused (include/gs_loss.h)
   depth_loss.py   the reference's masked depth-correlation (Pearson) loss, fused (include/gs_depth_loss.h)
+  robust_loss.py  the reference's quantile-trimmed squared losses and a batched exact quantile: radix select,
+                  no sort (include/gs_robust_loss.h)
   resample.py     the reference's bilinear F.interpolate to a prior's size, deterministic (include/gs_resample.h)
   feature_loss.py the reference's feature-distillation loss: resample to the prior, then L1 (+ SSIM)
   densify.py      the reference's clone / split / prune with the Adam state (include/gs_densify.h)
@@ -32,6 +34,8 @@ from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer, Grad
 from ._C import set_default_compat, get_default_compat  # noqa: F401
 from .image_loss import photometric_image_loss, photometric_loss, photometric_loss_torch  # noqa: F401
 from .depth_loss import depth_correlation_loss, depth_correlation_loss_torch  # noqa: F401
+from .robust_loss import (masked_trimmed_mse_loss, masked_trimmed_mse_loss_torch, plane_quantile,  # noqa: F401
+                          plane_quantile_torch, trimmed_mse_loss, trimmed_mse_loss_torch)
 from .resample import bilinear_resize, bilinear_resize_torch  # noqa: F401
 from .feature_loss import distillation_image_loss, feature_distillation_loss  # noqa: F401
 # `densify` here is the function; its module (schedule, plan, classify_torch, ...) is

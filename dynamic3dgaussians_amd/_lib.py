@@ -74,6 +74,15 @@ class GsDepthLoss(ctypes.Structure):
                 ("workspace_bytes", ctypes.c_uint64)]
 
 
+class GsRobustLoss(ctypes.Structure):
+    """include/gs_robust_loss.h gs_robust_loss."""
+    _fields_ = [("B", c_int32), ("R", c_int32), ("N", c_int32), ("layout", c_int32), ("pred", c_void_p),
+                ("gt", c_void_p), ("mask", c_void_p), ("mask_batch_stride", c_int64), ("quantile", ctypes.c_double),
+                ("select", c_int32), ("over_masked", c_int32), ("normalize", c_int32), ("norm_width", c_int32),
+                ("skip_degenerate", c_int32), ("_pad", c_int32), ("losses", c_void_p), ("stats", c_void_p),
+                ("workspace", c_void_p), ("workspace_bytes", ctypes.c_uint64)]
+
+
 class GsResample(ctypes.Structure):
     """include/gs_resample.h gs_resample."""
     _fields_ = [("B", c_int32), ("Ch", c_int32), ("H", c_int32), ("W", c_int32), ("h", c_int32), ("w", c_int32),
@@ -348,6 +357,12 @@ PROTOTYPES = {
     "gs_depth_loss_validate": (ctypes.c_int, [ctypes.POINTER(GsDepthLoss), ctypes.c_int, c_void_p, c_void_p]),
     "gs_depth_loss_forward": (ctypes.c_int, [ctypes.POINTER(GsDepthLoss), c_void_p]),
     "gs_depth_loss_backward": (ctypes.c_int, [ctypes.POINTER(GsDepthLoss), c_void_p, c_void_p, c_void_p]),
+    # include/gs_robust_loss.h
+    "gs_robust_loss_struct_bytes": (c_size_t, []),
+    "gs_robust_loss_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32]),
+    "gs_robust_loss_validate": (ctypes.c_int, [ctypes.POINTER(GsRobustLoss), ctypes.c_int, c_void_p, c_void_p]),
+    "gs_robust_loss_forward": (ctypes.c_int, [ctypes.POINTER(GsRobustLoss), c_void_p]),
+    "gs_robust_loss_backward": (ctypes.c_int, [ctypes.POINTER(GsRobustLoss), c_void_p, c_void_p, c_void_p]),
     # include/gs_resample.h
     "gs_resample_struct_bytes": (c_size_t, []),
     "gs_resample_workspace_bytes": (c_size_t, [c_int32, c_int32]),
