@@ -17,6 +17,8 @@ Layout:
                   no sort (include/gs_robust_loss.h)
   resample.py     the reference's bilinear F.interpolate to a prior's size, deterministic (include/gs_resample.h)
   feature_loss.py the reference's feature-distillation loss: resample to the prior, then L1 (+ SSIM)
+  feature_decoder.py the reference's "speedup" 1x1 decoder fused with the L1 loss on the matrix cores
+                  (include/gs_feature_decoder.h)
   densify.py      the reference's clone / split / prune with the Adam state (include/gs_densify.h)
   scene_loss.py   the reference's floor / bg / soft_col_cons terms and its foreground split, no host syncs
                   (include/gs_scene_loss.h)
@@ -37,7 +39,9 @@ from .depth_loss import depth_correlation_loss, depth_correlation_loss_torch  # 
 from .robust_loss import (masked_trimmed_mse_loss, masked_trimmed_mse_loss_torch, plane_quantile,  # noqa: F401
                           plane_quantile_torch, trimmed_mse_loss, trimmed_mse_loss_torch)
 from .resample import bilinear_resize, bilinear_resize_torch  # noqa: F401
-from .feature_loss import distillation_image_loss, feature_distillation_loss  # noqa: F401
+from .feature_loss import decoded_distillation_loss, distillation_image_loss, feature_distillation_loss  # noqa: F401
+from .feature_decoder import (FeatureDecoder, decode_features, decode_features_torch, decoded_l1_loss,  # noqa: F401
+                              decoded_l1_loss_torch)
 # `densify` here is the function; its module (schedule, plan, classify_torch, ...) is
 # importlib.import_module('dynamic3dgaussians_amd.densify')
 from .densify import densify, densify_torch  # noqa: F401

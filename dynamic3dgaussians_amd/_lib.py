@@ -90,6 +90,21 @@ class GsResample(ctypes.Structure):
                 ("workspace_bytes", ctypes.c_uint64)]
 
 
+class GsFeatureDecoder(ctypes.Structure):
+    """include/gs_feature_decoder.h gs_feature_decoder."""
+    _fields_ = [("B", c_int32), ("F_in", c_int32), ("C_out", c_int32), ("h", c_int32), ("w", c_int32),
+                ("mask_per_camera", c_int32), ("x", c_void_p), ("weight", c_void_p), ("bias", c_void_p),
+                ("target", c_void_p), ("mask", c_void_p), ("up", c_void_p), ("d_y", c_void_p), ("y", c_void_p),
+                ("loss", c_void_p), ("d_x", c_void_p), ("d_weight", c_void_p), ("d_bias", c_void_p),
+                ("workspace", c_void_p), ("workspace_bytes", ctypes.c_uint64)]
+
+
+# include/gs_feature_decoder.h: the tile shape, the grid rule's block count, the limits and the passes
+FD_TILE_ROWS, FD_TILE_PIXELS, FD_GRID, FD_GRID_FORWARD = 32, 128, 512, 1024
+FD_MAX_F_IN, FD_MAX_C_OUT, FD_MAX_WEIGHTS = 64, 512, 16384
+FD_PASS_DECODE, FD_PASS_LOSS, FD_PASS_LOSS_BACKWARD, FD_PASS_BACKWARD = 0, 1, 2, 3
+
+
 class GsSceneLoss(ctypes.Structure):
     """include/gs_scene_loss.h gs_scene_loss."""
     _fields_ = [("P", c_int64), ("n_fg", c_int64), ("n_bg", c_int64), ("slot", c_void_p), ("means", c_void_p),
@@ -370,6 +385,17 @@ PROTOTYPES = {
     "gs_resample_axis": (ctypes.c_int, [c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "gs_resample_forward": (ctypes.c_int, [ctypes.POINTER(GsResample), c_void_p]),
     "gs_resample_backward": (ctypes.c_int, [ctypes.POINTER(GsResample), c_void_p, c_void_p, c_void_p]),
+    # include/gs_feature_decoder.h
+    "gs_feature_decoder_struct_bytes": (c_size_t, []),
+    "gs_feature_decoder_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32]),
+    "gs_feature_decoder_grid_x": (c_int32, [c_int32, c_int32, c_int32]),
+    "gs_feature_decoder_n_t": (c_int32, [c_int32]),
+    "gs_feature_decoder_n_acc": (c_int64, [c_int32, c_int32, c_int32]),
+    "gs_feature_decoder_validate": (ctypes.c_int, [ctypes.POINTER(GsFeatureDecoder), c_int32]),
+    "gs_feature_decoder_forward": (ctypes.c_int, [ctypes.POINTER(GsFeatureDecoder), c_void_p]),
+    "gs_feature_decoder_loss_forward": (ctypes.c_int, [ctypes.POINTER(GsFeatureDecoder), c_void_p]),
+    "gs_feature_decoder_loss_backward": (ctypes.c_int, [ctypes.POINTER(GsFeatureDecoder), c_void_p]),
+    "gs_feature_decoder_backward": (ctypes.c_int, [ctypes.POINTER(GsFeatureDecoder), c_void_p]),
     # include/gs_scene_loss.h
     "gs_scene_loss_struct_bytes": (c_size_t, []),
     "gs_scene_loss_workspace_bytes": (c_size_t, [c_int64]),
