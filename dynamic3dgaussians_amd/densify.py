@@ -33,11 +33,12 @@ that have no GPU.  The HIP path has no CPU fallback: host tensors raise.
 from __future__ import annotations
 
 import ctypes
+import functools
 from typing import Optional
 
 import torch
 
-from . import _lib
+from . import _args, _lib
 from ._lib import GsplatError
 
 N_SPLIT = _lib.GS_DENSIFY_N_SPLIT
@@ -61,18 +62,7 @@ def schedule(i: int) -> dict:
 
 
 def _need(t, name: str, rows: Optional[int] = None) -> torch.Tensor:
-    if not isinstance(t, torch.Tensor):
-        raise GsplatError(f"{name} must be a tensor")
-    if not t.is_cuda:
-        raise GsplatError(f"the HIP densification needs device tensors ({name} is on the CPU); "
-                          "densify_torch runs anywhere")
-    if t.dtype != torch.float32:
-        raise GsplatError(f"{name} must be float32 (got {t.dtype})")
-    if not t.is_contiguous():
-        raise GsplatError(f"{name} must be contiguous")
-    if rows is not None and (t.dim() < 1 or t.shape[0] != rows):
-        raise GsplatError(f"{name} must have {rows} rows (got shape {tuple(t.shape)})")
-    return t
+    return _args.need(t, name, rows=rows, op="densification needs", twin="densify_torch runs")
 
 
 def _device(t: torch.Tensor) -> torch.device:
@@ -239,7 +229,7 @@ def _hip_pass(params, variables, optimizer, sch, noise, generator, grad_thresh):
         dst = torch.empty((P_new,) + tuple(src.shape[1:]), dtype=torch.float32, device=dev)
         dm, dv = (torch.empty_like(dst), torch.empty_like(dst)) if m is not None else (None, None)
         width = src.numel() // P if P else max(1, int(torch.Size(src.shape[1:]).numel()))
-        p = lambda t: t.data_ptr() if (t is not None and t.numel()) else None  # noqa: E731
+        p = functools.partial(_args.ptr, empty_is_null=True)
         tk = args.t[n]
         tk.src, tk.src_exp_avg, tk.src_exp_avg_sq = p(src), p(m), p(v)
         tk.dst, tk.dst_exp_avg, tk.dst_exp_avg_sq = p(dst), p(dm), p(dv)

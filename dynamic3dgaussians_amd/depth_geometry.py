@@ -44,11 +44,12 @@ align_corners=True, which its call states, and the oracle is torch's grid_sample
 """
 from __future__ import annotations
 
+import functools
 from typing import Optional, Sequence, Tuple
 
 import torch
 
-from . import _lib
+from . import _args, _lib
 from ._lib import GsplatError
 
 FLOW_MIN_Z = 1e-7  # ideaII.py:132: points_2d[:, 2:].clamp(min=1e-7)
@@ -56,20 +57,7 @@ FLOW_MIN_Z = 1e-7  # ideaII.py:132: points_2d[:, 2:].clamp(min=1e-7)
 
 # ---- argument checks
 
-def _need(t, name: str, shape=None) -> torch.Tensor:
-    """metrics._need: what the kernels cannot take raises."""
-    if not isinstance(t, torch.Tensor):
-        raise GsplatError(f"{name} must be a tensor")
-    if not t.is_cuda:
-        raise GsplatError(f"the HIP depth geometry needs device tensors ({name} is on the CPU); "
-                          "the _torch twins run anywhere")
-    if t.dtype != torch.float32:
-        raise GsplatError(f"{name} must be float32 (got {t.dtype})")
-    if not t.is_contiguous():
-        raise GsplatError(f"{name} must be contiguous")
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise GsplatError(f"{name} must have shape {tuple(shape)} (got {tuple(t.shape)})")
-    return t
+_need = functools.partial(_args.need, op="depth geometry needs", twin="the _torch twins run")
 
 
 def _mats(m, name: str, n: int) -> Tuple[torch.Tensor, bool]:

@@ -27,36 +27,25 @@ computes it.
 """
 from __future__ import annotations
 
+import functools
 import math
 from typing import Optional
 
 import torch
 
-from . import _lib
+from . import _args, _lib
 from ._lib import GsplatError
 
 NEAR, FAR = 1e-7, 50.0  # dyn_train.py:20
 STATS = ("n", "mean_p", "mean_g", "Sxx", "Syy", "Sxy", "r", "valid")  # stats[b, 0:8]
 
 
-def _need(t, name: str, shape=None) -> torch.Tensor:
-    if not isinstance(t, torch.Tensor):
-        raise GsplatError(f"{name} must be a tensor")
-    if not t.is_cuda:
-        raise GsplatError(f"the HIP depth-correlation loss needs device tensors ({name} is on the CPU); "
-                          "depth_correlation_loss_torch runs anywhere")
-    if t.dtype != torch.float32:
-        raise GsplatError(f"{name} must be float32 (got {t.dtype})")
-    if not t.is_contiguous():
-        raise GsplatError(f"{name} must be contiguous")
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise GsplatError(f"{name} must have shape {tuple(shape)} (got {tuple(t.shape)})")
-    return t
+_need = functools.partial(_args.need, op="depth-correlation loss needs", twin="depth_correlation_loss_torch runs")
 
 
 def _struct(depth, target, mask, near, far, skip, losses, stats, ws):
     B, H, W = depth.shape
-    p = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    p = _args.ptr
     return _lib.GsDepthLoss(B=B, H=H, W=W, depth=p(depth), target=p(target), mask=p(mask),
                             mask_batch_stride=H * W if mask is not None and mask.dim() == 3 else 0,
                             near=near, far=far, skip_degenerate=int(skip), losses=p(losses), stats=p(stats),
@@ -95,11 +84,6 @@ class _DepthCorrelationLoss(torch.autograd.Function):
         return d_depth, None, None, None, None, None
 
 
-def _check_reduction(reduction: str):
-    if reduction not in ("sum", "none"):
-        raise ValueError(f"reduction must be 'sum' or 'none' (got {reduction!r})")
-
-
 def _planes(depth, what="depth"):
     """[B, 1, H, W], [B, H, W] or [H, W] -> ([B, H, W] view, single)."""
     if not isinstance(depth, torch.Tensor) or depth.dim() not in (2, 3, 4) or (depth.dim() == 4 and depth.shape[1] != 1):
@@ -124,7 +108,7 @@ def depth_correlation_loss(depth: torch.Tensor, target: torch.Tensor, mask: Opti
     degenerate: its loss is NaN as in the reference, or 0 with an all-zero gradient plane under
     skip_degenerate=True; the other cameras are unaffected.  return_stats=True also returns the
     per-camera statistics [B, 8] = (n, mean p, mean g, Sxx, Syy, Sxy, unclamped r, valid)."""
-    _check_reduction(reduction)
+    _args.check_reduction(reduction)
     d3, single = _planes(depth)
     _need(depth, "depth")
     _need(target, "target", depth.shape)
@@ -133,19 +117,12 @@ def depth_correlation_loss(depth: torch.Tensor, target: torch.Tensor, mask: Opti
     B, H, W = d3.shape
     if min(B, H, W) < 1:
         raise GsplatError(f"depth must not be empty (got {tuple(depth.shape)})")
-    if mask is not None:
-        if not isinstance(mask, torch.Tensor) or not mask.is_cuda:
-            raise GsplatError("mask must be a device tensor")
-        if tuple(mask.shape) not in ((H, W), (B, H, W)):
-            raise GsplatError(f"mask must have shape {(H, W)} or {(B, H, W)} (got {tuple(mask.shape)})")
-        if mask.dtype != torch.uint8:
-            mask = (mask != 0).to(torch.uint8)
-        mask = mask.detach().contiguous()
+    mask = _args.mask_u8(mask, B, H, W)
     near, far = float(near), float(far)
     if not (math.isfinite(near) and math.isfinite(far) and 0.0 < near < far):
         raise GsplatError(f"near and far must be finite with 0 < near < far (got {near}, {far})")
     losses, stats = _DepthCorrelationLoss.apply(d3, target.reshape(B, H, W), mask, near, far, bool(skip_degenerate))
-    out = losses.sum() if reduction == "sum" else (losses[0] if single else losses)
+    out = _args.reduce_losses(losses, reduction, single)
     return (out, stats) if return_stats else out
 
 
@@ -168,7 +145,7 @@ def depth_correlation_loss_torch(depth: torch.Tensor, target: torch.Tensor, mask
     computes 0/0; whether that comes out as NaN or as noise depends there on how the mean of a
     constant rounds, so it is pinned here: NaN, with a NaN gradient where one would flow, or 0
     with a zero gradient under skip_degenerate=True."""
-    _check_reduction(reduction)
+    _args.check_reduction(reduction)
     d3, single = _planes(depth)
     g3, _ = _planes(target, "target")
     B, H, W = d3.shape
@@ -201,5 +178,5 @@ def depth_correlation_loss_torch(depth: torch.Tensor, target: torch.Tensor, mask
                                       gt.detach().mean() if n else zero + float("nan"), sxx, syy, sxy, r,
                                       zero + float(valid)]))
     losses = torch.stack(losses)
-    out = losses.sum() if reduction == "sum" else (losses[0] if single else losses)
+    out = _args.reduce_losses(losses, reduction, single)
     return (out, torch.stack(stats)) if return_stats else out

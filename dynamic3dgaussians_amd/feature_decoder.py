@@ -33,7 +33,7 @@ from typing import Optional
 
 import torch
 
-from . import _lib
+from . import _args, _lib
 from ._lib import GsplatError
 
 MAX_F_IN, MAX_C_OUT, MAX_WEIGHTS = _lib.FD_MAX_F_IN, _lib.FD_MAX_C_OUT, _lib.FD_MAX_WEIGHTS
@@ -80,11 +80,8 @@ def _shapes(x, weight, bias, target=None, mask=None):
 
 
 def _reduce(loss, reduction):
-    if reduction == "sum":
-        return loss.sum()
-    if reduction == "none":
-        return loss
-    raise GsplatError(f"reduction must be 'sum' or 'none' (got {reduction!r})")
+    _args.check_reduction(reduction, GsplatError)
+    return loss.sum() if reduction == "sum" else loss
 
 
 def decode_features_torch(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -111,15 +108,8 @@ def decoded_l1_loss_torch(x: torch.Tensor, weight: torch.Tensor, bias: Optional[
 
 def _device_checks(**tensors):
     for name, t in tensors.items():
-        if t is None:
-            continue
-        if not t.is_cuda:
-            raise GsplatError(f"the HIP feature decoder needs device tensors ({name} is on the CPU); "
-                              "decode_features_torch / decoded_l1_loss_torch run anywhere")
-        if t.dtype != torch.float32:
-            raise GsplatError(f"{name} must be float32 (got {t.dtype})")
-        if not t.is_contiguous():
-            raise GsplatError(f"{name} must be contiguous")
+        if t is not None:
+            _args.need(t, name, op="feature decoder needs", twin="decode_features_torch / decoded_l1_loss_torch run")
 
 
 def _limits(F_in, C_out):
@@ -131,7 +121,7 @@ def _limits(F_in, C_out):
 
 def _struct(x4, C_out, ws, **ptrs):
     B, F_in, h, w = x4.shape
-    p = {k: (v.data_ptr() if v is not None else None) for k, v in ptrs.items()}
+    p = {k: _args.ptr(v) for k, v in ptrs.items()}
     return _lib.GsFeatureDecoder(B=B, F_in=F_in, C_out=C_out, h=h, w=w, x=x4.data_ptr(), workspace=ws.data_ptr(),
                                  workspace_bytes=ws.numel(), **p)
 
@@ -235,8 +225,7 @@ def decoded_l1_loss(x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.
     >= 0.  reduction="sum": the sum over the cameras (the TimestepDriver.image_loss convention);
     "none": [B].  Contiguous float32 device tensors only; differentiable in x, weight and bias;
     deterministic."""
-    if reduction not in ("sum", "none"):
-        raise GsplatError(f"reduction must be 'sum' or 'none' (got {reduction!r})")
+    _args.check_reduction(reduction, GsplatError)
     x4, w2, t4, m = _shapes(x, weight, bias, target, mask)
     _device_checks(x=x, weight=weight, bias=bias, target=target, mask=mask)
     _limits(x4.shape[1], w2.shape[0])

@@ -23,36 +23,25 @@ tensors raise.
 """
 from __future__ import annotations
 
+import functools
 import math
 from typing import Optional
 
 import torch
 
-from . import _lib
+from . import _args, _lib
 from ._lib import GsplatError
 
 WINDOW, SIGMA = 11, 1.5
 C1, C2 = 0.01 ** 2, 0.03 ** 2
 
 
-def _need(t, name: str, shape=None) -> torch.Tensor:
-    if not isinstance(t, torch.Tensor):
-        raise GsplatError(f"{name} must be a tensor")
-    if not t.is_cuda:
-        raise GsplatError(f"the HIP photometric loss needs device tensors ({name} is on the CPU); "
-                          "photometric_loss_torch runs anywhere")
-    if t.dtype != torch.float32:
-        raise GsplatError(f"{name} must be float32 (got {t.dtype})")
-    if not t.is_contiguous():
-        raise GsplatError(f"{name} must be contiguous")
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise GsplatError(f"{name} must have shape {tuple(shape)} (got {tuple(t.shape)})")
-    return t
+_need = functools.partial(_args.need, op="photometric loss needs", twin="photometric_loss_torch runs")
 
 
 def _struct(image, target, mask, gain, offset, l1_weight, ssim_weight, losses, ws):
     B, Ch, H, W = image.shape
-    p = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    p = _args.ptr
     return _lib.GsPhotoLoss(B=B, Ch=Ch, H=H, W=W, image=p(image), target=p(target), mask=p(mask), gain=p(gain),
                             offset=p(offset),
                             mask_batch_stride=H * W if mask is not None and mask.dim() == 3 else 0,
@@ -99,11 +88,6 @@ class _PhotometricLoss(torch.autograd.Function):
         return d_image, None, None, d_gain, d_offset, None, None
 
 
-def _check_reduction(reduction: str):
-    if reduction not in ("sum", "none"):
-        raise ValueError(f"reduction must be 'sum' or 'none' (got {reduction!r})")
-
-
 def photometric_loss(image: torch.Tensor, target: torch.Tensor, mask: Optional[torch.Tensor] = None,
                      gain: Optional[torch.Tensor] = None, offset: Optional[torch.Tensor] = None,
                      l1_weight: float = 0.8, ssim_weight: float = 0.2, reduction: str = "sum") -> torch.Tensor:
@@ -113,7 +97,7 @@ def photometric_loss(image: torch.Tensor, target: torch.Tensor, mask: Optional[t
     (reduction="none").  gain / offset [B, Ch] ([Ch] for one image) and mask [H, W] or [B, H, W]
     are optional.  Contiguous float32 device tensors only (a mask of another dtype is converted).
     Differentiable in image, gain and offset; deterministic forward and backward."""
-    _check_reduction(reduction)
+    _args.check_reduction(reduction)
     if not isinstance(image, torch.Tensor) or image.dim() not in (3, 4):
         raise GsplatError("image must be a [B, Ch, H, W] or [Ch, H, W] tensor")
     single = image.dim() == 3
@@ -126,12 +110,7 @@ def photometric_loss(image: torch.Tensor, target: torch.Tensor, mask: Optional[t
     B, Ch, H, W = image.shape
     if min(B, Ch, H, W) < 1:
         raise GsplatError(f"image must not be empty (got {tuple(image.shape)})")
-    if mask is not None:
-        if not isinstance(mask, torch.Tensor) or not mask.is_cuda:
-            raise GsplatError("mask must be a device tensor")
-        if tuple(mask.shape) not in ((H, W), (B, H, W)):
-            raise GsplatError(f"mask must have shape {(H, W)} or {(B, H, W)} (got {tuple(mask.shape)})")
-        mask = mask.to(torch.float32).contiguous()
+    mask = _args.mask_f32(mask, B, H, W)
     if (gain is None) != (offset is None):  # the kernel takes both or neither
         other = offset if gain is None else gain
         if gain is None:
@@ -146,7 +125,7 @@ def photometric_loss(image: torch.Tensor, target: torch.Tensor, mask: Optional[t
     if not math.isfinite(l1_weight) or not math.isfinite(ssim_weight):
         raise GsplatError("l1_weight and ssim_weight must be finite")
     losses = _PhotometricLoss.apply(image, target, mask, gain, offset, float(l1_weight), float(ssim_weight))
-    return losses.sum() if reduction == "sum" else (losses[0] if single else losses)
+    return _args.reduce_losses(losses, reduction, single)
 
 
 def photometric_image_loss(im, target, *, cam_m: Optional[torch.Tensor] = None,
@@ -192,7 +171,7 @@ def photometric_loss_torch(image: torch.Tensor, target: torch.Tensor, mask: Opti
                            l1_weight: float = 0.8, ssim_weight: float = 0.2, reduction: str = "sum") -> torch.Tensor:
     """photometric_loss in PyTorch operations, any device and dtype: five zero-padded depthwise
     convolutions per call and autograd for the backward, as the reference computes it."""
-    _check_reduction(reduction)
+    _args.check_reduction(reduction)
     single = image.dim() == 3
     if single:
         image, target = image[None], target[None]
@@ -220,4 +199,4 @@ def photometric_loss_torch(image: torch.Tensor, target: torch.Tensor, mask: Opti
     s12 = blur(x * y) - mu12
     ssim_map = ((2 * mu12 + C1) * (2 * s12 + C2)) / ((mu1_sq + mu2_sq + C1) * (s1 + s2 + C2))
     losses = l1_weight * l1 + ssim_weight * (1 - ssim_map.mean(dim=(1, 2, 3)))
-    return losses.sum() if reduction == "sum" else (losses[0] if single else losses)
+    return _args.reduce_losses(losses, reduction, single)

@@ -46,32 +46,20 @@ package) and the image file unproject_image saves of its estimated depth map
 """
 from __future__ import annotations
 
+import functools
 import math
 from typing import Callable, Iterable, NamedTuple, Optional, Tuple
 
 import torch
 
-from . import _lib
+from . import _args, _lib
 from ._lib import GsplatError
 
 WINDOW, SIGMA = 11, 1.5
 C1, C2 = 0.01 ** 2, 0.03 ** 2
 
 
-def _need(t, name: str, shape=None) -> torch.Tensor:
-    """image_loss._need for the metrics: what the kernels cannot take raises."""
-    if not isinstance(t, torch.Tensor):
-        raise GsplatError(f"{name} must be a tensor")
-    if not t.is_cuda:
-        raise GsplatError(f"the HIP metrics need device tensors ({name} is on the CPU); "
-                          "image_metrics_torch / mask_iou_torch run anywhere")
-    if t.dtype != torch.float32:
-        raise GsplatError(f"{name} must be float32 (got {t.dtype})")
-    if not t.is_contiguous():
-        raise GsplatError(f"{name} must be contiguous")
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise GsplatError(f"{name} must have shape {tuple(shape)} (got {tuple(t.shape)})")
-    return t
+_need = functools.partial(_args.need, op="metrics need", twin="image_metrics_torch / mask_iou_torch run")
 
 
 class ImageMetrics(NamedTuple):
@@ -98,11 +86,10 @@ def _check_pair(pred, target, mask, need):
     B, Ch, H, W = pred.shape
     if min(B, Ch, H, W) < 1:
         raise GsplatError(f"pred must not be empty (got {tuple(pred.shape)})")
-    if mask is not None:
-        if not isinstance(mask, torch.Tensor) or (need and not mask.is_cuda):
-            raise GsplatError("mask must be a device tensor")
-        if tuple(mask.shape) not in ((H, W), (B, H, W)):
-            raise GsplatError(f"mask must have shape {(H, W)} or {(B, H, W)} (got {tuple(mask.shape)})")
+    if need:
+        mask = _args.mask_f32(mask, B, H, W)
+    elif mask is not None:
+        _args.check_mask(mask, B, H, W, need_device=False)
     return pred, target, mask, single
 
 
@@ -121,8 +108,6 @@ def image_metrics(pred: torch.Tensor, target: torch.Tensor, mask: Optional[torch
     L = _lib.load()
     dev = pred.device
     pred, target = pred.detach(), target.detach()
-    if mask is not None:
-        mask = mask.detach().to(torch.float32).contiguous()
     out = torch.empty(B, 4, dtype=torch.float32, device=dev)
     ws = torch.empty(L.gs_image_metrics_workspace_bytes(B, Ch, H, W), dtype=torch.uint8, device=dev)
     args = _lib.GsImageMetrics(B=B, Ch=Ch, H=H, W=W, pred=pred.data_ptr(), target=target.data_ptr(),

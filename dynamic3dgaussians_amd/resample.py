@@ -41,7 +41,7 @@ import functools
 import numpy as np
 import torch
 
-from . import _lib
+from . import _args, _lib
 from ._lib import GsplatError
 
 MAX_SIZE = 32768  # per axis, include/gs_resample.h
@@ -100,7 +100,7 @@ def _planes(x):
 
 
 def _struct(B, Ch, H, W, h, w, align, x=None, y=None, ws=None):
-    p = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    p = _args.ptr
     return _lib.GsResample(B=B, Ch=Ch, H=H, W=W, h=h, w=w, align_corners=int(align), x=p(x), y=p(y),
                            workspace=p(ws), workspace_bytes=ws.numel() if ws is not None else 0)
 
@@ -139,12 +139,7 @@ def bilinear_resize(x: torch.Tensor, size, align_corners: bool = False) -> torch
     forward and backward are deterministic.  Equal sizes give a bit-exact copy."""
     h, w = _size(size)
     x4 = _planes(x)
-    if not x.is_cuda:
-        raise GsplatError("the HIP resample needs device tensors (x is on the CPU); bilinear_resize_torch runs anywhere")
-    if x.dtype != torch.float32:
-        raise GsplatError(f"x must be float32 (got {x.dtype})")
-    if not x.is_contiguous():
-        raise GsplatError("x must be contiguous")
+    _args.need(x, "x", op="resample needs", twin="bilinear_resize_torch runs")
     y = _BilinearResize.apply(x4, h, w, bool(align_corners))
     return y.reshape(*x.shape[:-2], h, w)
 

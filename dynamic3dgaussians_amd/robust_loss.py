@@ -30,31 +30,20 @@ how the kernels round.
 """
 from __future__ import annotations
 
+import functools
 import math
 from typing import Optional
 
 import torch
 
-from . import _lib
+from . import _args, _lib
 from ._lib import GsplatError
 
 STATS = ("thr", "kept", "kept_masked", "nan")  # stats[b, 0:4], float64
 CHANNELS, ROWS, VALUES = 0, 1, 2  # include/gs_robust_loss.h
 
 
-def _need(t, name: str, shape=None) -> torch.Tensor:
-    if not isinstance(t, torch.Tensor):
-        raise GsplatError(f"{name} must be a tensor")
-    if not t.is_cuda:
-        raise GsplatError(f"the HIP robust losses need device tensors ({name} is on the CPU); "
-                          "the _torch twins run anywhere")
-    if t.dtype != torch.float32:
-        raise GsplatError(f"{name} must be float32 (got {t.dtype})")
-    if not t.is_contiguous():
-        raise GsplatError(f"{name} must be contiguous")
-    if shape is not None and tuple(t.shape) != tuple(shape):
-        raise GsplatError(f"{name} must have shape {tuple(shape)} (got {tuple(t.shape)})")
-    return t
+_need = functools.partial(_args.need, op="robust losses need", twin="the _torch twins run")
 
 
 def _check_q(q) -> float:
@@ -62,11 +51,6 @@ def _check_q(q) -> float:
     if not (math.isfinite(q) and 0.0 <= q <= 1.0):
         raise GsplatError(f"quantile must be in [0, 1] (got {q})")
     return q
-
-
-def _check_reduction(reduction: str):
-    if reduction not in ("sum", "none"):
-        raise ValueError(f"reduction must be 'sum' or 'none' (got {reduction!r})")
 
 
 def _check_over(quantile_over: str):
@@ -81,7 +65,7 @@ def _check_int32(B: int, N: int):
 
 def _struct(cfg, pred, gt, mask, losses, stats, ws):
     layout, B, R, N, q, select, over_masked, normalize, width, skip = cfg
-    p = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    p = _args.ptr
     return _lib.GsRobustLoss(B=B, R=R, N=N, layout=layout, pred=p(pred), gt=p(gt), mask=p(mask),
                              mask_batch_stride=N if mask is not None and mask.dim() == 2 else 0, quantile=q,
                              select=int(select), over_masked=int(over_masked), normalize=int(normalize),
@@ -145,15 +129,9 @@ def plane_quantile(x: torch.Tensor, q: float) -> torch.Tensor:
 
 
 def _mask_bytes(mask, B, H, W):
+    mask = _args.mask_u8(mask, B, H, W)
     if mask is None:
         return None
-    if not isinstance(mask, torch.Tensor) or not mask.is_cuda:
-        raise GsplatError("mask must be a device tensor")
-    if tuple(mask.shape) not in ((H, W), (B, H, W)):
-        raise GsplatError(f"mask must have shape {(H, W)} or {(B, H, W)} (got {tuple(mask.shape)})")
-    if mask.dtype != torch.uint8:
-        mask = (mask != 0).to(torch.uint8)
-    mask = mask.detach().contiguous()
     return mask.reshape(-1) if mask.dim() == 2 else mask.reshape(B, -1)
 
 
@@ -183,7 +161,7 @@ def masked_trimmed_mse_loss(pred: torch.Tensor, gt: torch.Tensor, mask: Optional
     A camera with no kept pixel gives NaN with normalize=False (0 with a zero gradient under
     skip_degenerate=True) and 0 with normalize=True; the other cameras are unaffected.
     return_stats=True also returns [B, 4] float64 = (thr, kept count, sum kept m, NaN count)."""
-    _check_reduction(reduction)
+    _args.check_reduction(reduction)
     _check_over(quantile_over)
     p4, single = _images(pred)
     _need(pred, "pred")
@@ -199,7 +177,7 @@ def masked_trimmed_mse_loss(pred: torch.Tensor, gt: torch.Tensor, mask: Optional
     cfg = (CHANNELS, B, C, H * W, q, q < 1.0, quantile_over == "masked" and mask is not None, bool(normalize), W,
            bool(skip_degenerate))
     losses, stats = _RobustLoss.apply(p4.reshape(B, C, H * W), gt.reshape(B, C, H * W), mask, cfg)
-    out = losses.sum() if reduction == "sum" else (losses[0] if single else losses)
+    out = _args.reduce_losses(losses, reduction, single)
     return (out, stats) if return_stats else out
 
 
@@ -267,7 +245,7 @@ def masked_trimmed_mse_loss_torch(pred: torch.Tensor, gt: torch.Tensor, mask: Op
     """masked_trimmed_mse_loss in PyTorch operations, any device and dtype, camera by camera in the
     reference's order: the residual, the threshold, boolean indexing of (e * mask) by the kept
     set, the mean or the normalised sum; autograd for the backward."""
-    _check_reduction(reduction)
+    _args.check_reduction(reduction)
     _check_over(quantile_over)
     q = _check_q(quantile)
     p4, single = _images(pred)
@@ -296,7 +274,7 @@ def masked_trimmed_mse_loss_torch(pred: torch.Tensor, gt: torch.Tensor, mask: Op
         if return_stats:
             stats.append(torch.stack([thr, cnt.double(), cm.double(), (torch.isnan(e.detach()) & part).sum().double()]))
     losses = torch.stack(losses)
-    out = losses.sum() if reduction == "sum" else (losses[0] if single else losses)
+    out = _args.reduce_losses(losses, reduction, single)
     return (out, torch.stack(stats)) if return_stats else out
 
 

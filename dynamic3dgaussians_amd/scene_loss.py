@@ -36,11 +36,12 @@ The HIP path has no CPU fallback: host tensors raise.
 """
 from __future__ import annotations
 
+import functools
 from typing import Callable, Dict, Optional
 
 import torch
 
-from . import _lib
+from . import _args, _lib
 from ._lib import GsplatError
 from .neighbor import neighbor_losses
 
@@ -89,18 +90,8 @@ def foreground_split(is_fg: torch.Tensor, variables: Optional[dict] = None) -> F
 
 
 def _need(t, name: str, shape, dtype=torch.float32) -> torch.Tensor:
-    if not isinstance(t, torch.Tensor):
-        raise GsplatError(f"{name} must be a tensor")
-    if not t.is_cuda:
-        raise GsplatError(f"the HIP scene losses need device tensors ({name} is on the CPU); "
-                          "regularizer_losses_torch runs anywhere")
-    if t.dtype != dtype:
-        raise GsplatError(f"{name} must be {dtype} (got {t.dtype})")
-    if tuple(t.shape) != tuple(shape):
-        raise GsplatError(f"{name} must have shape {tuple(shape)} (got {tuple(t.shape)})")
-    if not t.is_contiguous():
-        raise GsplatError(f"{name} must be contiguous")
-    return t
+    return _args.need(t, name, shape, dtype=dtype, shape_first=True, op="scene losses need",
+                      twin="regularizer_losses_torch runs")
 
 
 def _need_split(split, P: int) -> ForegroundSplit:
@@ -112,8 +103,7 @@ def _need_split(split, P: int) -> ForegroundSplit:
     return split
 
 
-def _ptr(t):
-    return t.data_ptr() if t is not None and t.numel() else None
+_ptr = functools.partial(_args.ptr, empty_is_null=True)
 
 
 class _GatherForeground(torch.autograd.Function):

@@ -163,7 +163,10 @@ def test_build_lists_the_new_sources():
     for f in ("gs_feature_decoder.hip", "gs_feature_decoder_host.cpp", "gs_feature_decoder_layout.h", "gs_split_mfma.h"):
         assert os.path.exists(os.path.join(build.CSRC, f))
     with open(os.path.join(build.CSRC, "gs_render.hip")) as fh:
-        assert "gs_split_mfma.h" not in fh.read()  # the render keeps its own copy of the split helpers
+        render = fh.read()
+    assert '#include "gs_split_mfma.h"' in render  # one home for the split helpers
+    for definition in ("void split_bf16(", "struct bsplit", "struct hsplit"):
+        assert definition not in render
 
 
 def test_ctypes_mirror_and_documented_constants():
