@@ -19,6 +19,8 @@ Layout:
   feature_loss.py the reference's feature-distillation loss: resample to the prior, then L1 (+ SSIM)
   feature_decoder.py the reference's "speedup" 1x1 decoder fused with the L1 loss on the matrix cores
                   (include/gs_feature_decoder.h)
+  feature_pca.py  the reference's PCA colouring of feature maps: moments on the matrix cores, an on-device
+                  eigensolve, project / range / colour (include/gs_feature_pca.h)
   densify.py      the reference's clone / split / prune with the Adam state (include/gs_densify.h)
   scene_loss.py   the reference's floor / bg / soft_col_cons terms and its foreground split, no host syncs
                   (include/gs_scene_loss.h)
@@ -42,6 +44,9 @@ from .resample import bilinear_resize, bilinear_resize_torch  # noqa: F401
 from .feature_loss import decoded_distillation_loss, distillation_image_loss, feature_distillation_loss  # noqa: F401
 from .feature_decoder import (FeatureDecoder, decode_features, decode_features_torch, decoded_l1_loss,  # noqa: F401
                               decoded_l1_loss_torch)
+from .feature_pca import (FeaturePCA, FeaturePCATorch, feature_map, feature_map_pca, feature_map_torch,  # noqa: F401
+                          fit_sequence, fit_sequence_torch, pca_colour, pca_colour_torch, pca_covariance_torch,
+                          pca_eig_torch, pca_moments_torch, pca_project, pca_project_torch, pca_range_torch)
 # `densify` here is the function; its module (schedule, plan, classify_torch, ...) is
 # importlib.import_module('dynamic3dgaussians_amd.densify')
 from .densify import densify, densify_torch  # noqa: F401

@@ -105,6 +105,26 @@ FD_MAX_F_IN, FD_MAX_C_OUT, FD_MAX_WEIGHTS = 64, 512, 16384
 FD_PASS_DECODE, FD_PASS_LOSS, FD_PASS_LOSS_BACKWARD, FD_PASS_BACKWARD = 0, 1, 2, 3
 
 
+class GsFeaturePca(ctypes.Structure):
+    """include/gs_feature_pca.h gs_feature_pca."""
+    _fields_ = [("B", c_int32), ("C", c_int32), ("H", c_int32), ("W", c_int32), ("k", c_int32),
+                ("mask_per_image", c_int32), ("normalize", c_int32), ("sample_stride", c_int32), ("ddof", c_int32),
+                ("compute_shift", c_int32), ("out_uint8", c_int32), ("clamp", c_int32),
+                ("x", c_void_p), ("mask", c_void_p), ("shift", c_void_p), ("state", c_void_p), ("mean", c_void_p),
+                ("cov", c_void_p), ("evals", c_void_p), ("evecs", c_void_p), ("components", c_void_p),
+                ("components_f32", c_void_p), ("mean_f32", c_void_p), ("status", c_void_p),
+                ("proj_components", c_void_p), ("proj_mean", c_void_p), ("t", c_void_p), ("tmin", c_void_p),
+                ("tmax", c_void_p), ("sub", c_void_p), ("u", c_void_p), ("lo", c_void_p), ("hi", c_void_p),
+                ("out", c_void_p), ("workspace", c_void_p), ("workspace_bytes", ctypes.c_uint64)]
+
+
+# include/gs_feature_pca.h: the limits, the sweep cap, the tile and slab sizes and the passes
+FPCA_MAX_C, FPCA_MAX_K, FPCA_MAX_SWEEPS = 128, 8, 24
+FPCA_TILE_PIXELS, FPCA_CHUNK, FPCA_SLAB_GROUP, FPCA_LDS_MAX_C = 128, 4096, 64, 64
+(FPCA_PASS_UPDATE, FPCA_PASS_COVARIANCE, FPCA_PASS_FIT, FPCA_PASS_PROJECT, FPCA_PASS_OFFSET,
+ FPCA_PASS_COLOUR) = range(6)
+
+
 class GsSceneLoss(ctypes.Structure):
     """include/gs_scene_loss.h gs_scene_loss."""
     _fields_ = [("P", c_int64), ("n_fg", c_int64), ("n_bg", c_int64), ("slot", c_void_p), ("means", c_void_p),
@@ -396,6 +416,20 @@ PROTOTYPES = {
     "gs_feature_decoder_loss_forward": (ctypes.c_int, [ctypes.POINTER(GsFeatureDecoder), c_void_p]),
     "gs_feature_decoder_loss_backward": (ctypes.c_int, [ctypes.POINTER(GsFeatureDecoder), c_void_p]),
     "gs_feature_decoder_backward": (ctypes.c_int, [ctypes.POINTER(GsFeatureDecoder), c_void_p]),
+    # include/gs_feature_pca.h
+    "gs_feature_pca_struct_bytes": (c_size_t, []),
+    "gs_feature_pca_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32]),
+    "gs_feature_pca_n_acc": (c_int64, [c_int32, c_int32, c_int32]),
+    "gs_feature_pca_max_sweeps": (c_int32, []),
+    "gs_feature_pca_validate": (ctypes.c_int, [ctypes.POINTER(GsFeaturePca), c_int32]),
+    "gs_feature_pca_eig_host": (ctypes.c_int, [c_int32, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_int32),
+                                               ctypes.POINTER(c_int64)]),
+    "gs_feature_pca_update": (ctypes.c_int, [ctypes.POINTER(GsFeaturePca), c_void_p]),
+    "gs_feature_pca_covariance": (ctypes.c_int, [ctypes.POINTER(GsFeaturePca), c_void_p]),
+    "gs_feature_pca_fit": (ctypes.c_int, [ctypes.POINTER(GsFeaturePca), c_void_p]),
+    "gs_feature_pca_project": (ctypes.c_int, [ctypes.POINTER(GsFeaturePca), c_void_p]),
+    "gs_feature_pca_offset": (ctypes.c_int, [ctypes.POINTER(GsFeaturePca), c_void_p]),
+    "gs_feature_pca_colour": (ctypes.c_int, [ctypes.POINTER(GsFeaturePca), c_void_p]),
     # include/gs_scene_loss.h
     "gs_scene_loss_struct_bytes": (c_size_t, []),
     "gs_scene_loss_workspace_bytes": (c_size_t, [c_int64]),
