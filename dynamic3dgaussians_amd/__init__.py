@@ -21,6 +21,8 @@ Layout:
                   (include/gs_feature_decoder.h)
   feature_pca.py  the reference's PCA colouring of feature maps: moments on the matrix cores, an on-device
                   eigensolve, project / range / colour (include/gs_feature_pca.h)
+  feature_knn.py  exact cosine top-k neighbours in feature space: candidates on the matrix cores, an fp64 rerank
+                  with a certificate, an exhaustive fp64 search for the rest (include/gs_feature_knn.h)
   densify.py      the reference's clone / split / prune with the Adam state (include/gs_densify.h)
   scene_loss.py   the reference's floor / bg / soft_col_cons terms and its foreground split, no host syncs
                   (include/gs_scene_loss.h)
@@ -47,6 +49,8 @@ from .feature_decoder import (FeatureDecoder, decode_features, decode_features_t
 from .feature_pca import (FeaturePCA, FeaturePCATorch, feature_map, feature_map_pca, feature_map_torch,  # noqa: F401
                           fit_sequence, fit_sequence_torch, pca_colour, pca_colour_torch, pca_covariance_torch,
                           pca_eig_torch, pca_moments_torch, pca_project, pca_project_torch, pca_range_torch)
+from .feature_knn import (cosine_topk, feature_knn, feature_knn_candidates, feature_knn_torch,  # noqa: F401
+                          knn_affinity)
 # `densify` here is the function; its module (schedule, plan, classify_torch, ...) is
 # importlib.import_module('dynamic3dgaussians_amd.densify')
 from .densify import densify, densify_torch  # noqa: F401

@@ -125,6 +125,19 @@ FPCA_TILE_PIXELS, FPCA_CHUNK, FPCA_SLAB_GROUP, FPCA_LDS_MAX_C = 128, 4096, 64, 6
  FPCA_PASS_COLOUR) = range(6)
 
 
+class GsFeatureKnn(ctypes.Structure):
+    """include/gs_feature_knn.h gs_feature_knn_args."""
+    _fields_ = [("N", c_int32), ("M", c_int32), ("E", c_int32), ("k", c_int32), ("splits", c_int32), ("_pad", c_int32),
+                ("feats", c_void_p), ("queries", c_void_p), ("sim", c_void_p), ("index", c_void_p), ("stats", c_void_p),
+                ("cand_sim", c_void_p), ("cand_index", c_void_p), ("cand_count", c_void_p), ("cand_theta", c_void_p),
+                ("workspace", c_void_p), ("workspace_bytes", ctypes.c_uint64)]
+
+
+# include/gs_feature_knn.h: the limits, the scan's slack and its tile shape
+FKNN_MAX_E, FKNN_MAX_K, FKNN_MAX_ROWS, FKNN_MAX_SPLITS = 128, 32, 1 << 26, 32
+FKNN_SLACK, FKNN_ROW_BLOCK, FKNN_TILE = 16, 128, 32
+
+
 class GsSceneLoss(ctypes.Structure):
     """include/gs_scene_loss.h gs_scene_loss."""
     _fields_ = [("P", c_int64), ("n_fg", c_int64), ("n_bg", c_int64), ("slot", c_void_p), ("means", c_void_p),
@@ -430,6 +443,14 @@ PROTOTYPES = {
     "gs_feature_pca_project": (ctypes.c_int, [ctypes.POINTER(GsFeaturePca), c_void_p]),
     "gs_feature_pca_offset": (ctypes.c_int, [ctypes.POINTER(GsFeaturePca), c_void_p]),
     "gs_feature_pca_colour": (ctypes.c_int, [ctypes.POINTER(GsFeaturePca), c_void_p]),
+    # include/gs_feature_knn.h
+    "gs_feature_knn_struct_bytes": (c_size_t, []),
+    "gs_feature_knn_splits": (c_int32, [c_int32, c_int32, c_int32, c_int32]),
+    "gs_feature_knn_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32]),
+    "gs_feature_knn_bound": (ctypes.c_double, [c_int32]),
+    "gs_feature_knn_e_pad": (c_int32, [c_int32]),
+    "gs_feature_knn_validate": (ctypes.c_int, [ctypes.POINTER(GsFeatureKnn)]),
+    "gs_feature_knn": (ctypes.c_int, [ctypes.POINTER(GsFeatureKnn), c_void_p]),
     # include/gs_scene_loss.h
     "gs_scene_loss_struct_bytes": (c_size_t, []),
     "gs_scene_loss_workspace_bytes": (c_size_t, [c_int64]),
