@@ -23,6 +23,8 @@ Layout:
                   eigensolve, project / range / colour (include/gs_feature_pca.h)
   feature_knn.py  exact cosine top-k neighbours in feature space: candidates on the matrix cores, an fp64 rerank
                   with a certificate, an exhaustive fp64 search for the rest (include/gs_feature_knn.h)
+  spectral.py     spectral embedding and clustering of the feature kNN graph: Chebyshev-filtered subspace
+                  iteration, fp64, nothing read back (include/gs_spectral.h)
   densify.py      the reference's clone / split / prune with the Adam state (include/gs_densify.h)
   scene_loss.py   the reference's floor / bg / soft_col_cons terms and its foreground split, no host syncs
                   (include/gs_scene_loss.h)
@@ -74,5 +76,8 @@ from .motion_init import (KMeansResult, MotionInit, ProcrustesInit, cluster_medi
                           init_motion_coefs_from_features, kmeans, kmeans_assign, kmeans_assign_torch, kmeans_torch,
                           kmeans_update, kmeans_update_torch, solve_procrustes_bases,
                           solve_procrustes_bases_torch, velocity_directions)
+from .spectral import (SpectralClustering, SpectralEmbedding, graph_check, knn_graph, spectral_clustering,  # noqa: F401
+                       spectral_clustering_graph, spectral_embedding, spectral_embedding_dense,
+                       spectral_embedding_torch)
 
 __version__ = "0.1.0"

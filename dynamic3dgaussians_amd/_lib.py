@@ -138,6 +138,20 @@ FKNN_MAX_E, FKNN_MAX_K, FKNN_MAX_ROWS, FKNN_MAX_SPLITS = 128, 32, 1 << 26, 32
 FKNN_SLACK, FKNN_ROW_BLOCK, FKNN_TILE = 16, 128, 32
 
 
+class GsSpectral(ctypes.Structure):
+    """include/gs_spectral.h gs_spectral_args."""
+    _fields_ = [("n", c_int32), ("num_vectors", c_int32), ("nnz", c_int64), ("degree", c_int32),
+                ("max_outer", c_int32), ("row_normalize", c_int32), ("_pad", c_int32), ("seed", ctypes.c_uint64),
+                ("tol", ctypes.c_double), ("row_ptr", c_void_p), ("col", c_void_p), ("val", c_void_p),
+                ("eigenvalues", c_void_p), ("vectors", c_void_p), ("embedding", c_void_p), ("residuals", c_void_p),
+                ("status", c_void_p), ("workspace", c_void_p), ("workspace_bytes", ctypes.c_uint64)]
+
+
+# include/gs_spectral.h: the limits and the guard columns of the block
+SPECTRAL_MAX_K, SPECTRAL_MAX_N, SPECTRAL_MAX_DEGREE, SPECTRAL_MAX_OUTER = 64, 1 << 26, 64, 1000
+SPECTRAL_GUARD, SPECTRAL_MAX_B = 8, 72
+
+
 class GsSceneLoss(ctypes.Structure):
     """include/gs_scene_loss.h gs_scene_loss."""
     _fields_ = [("P", c_int64), ("n_fg", c_int64), ("n_bg", c_int64), ("slot", c_void_p), ("means", c_void_p),
@@ -451,6 +465,14 @@ PROTOTYPES = {
     "gs_feature_knn_e_pad": (c_int32, [c_int32]),
     "gs_feature_knn_validate": (ctypes.c_int, [ctypes.POINTER(GsFeatureKnn)]),
     "gs_feature_knn": (ctypes.c_int, [ctypes.POINTER(GsFeatureKnn), c_void_p]),
+    # include/gs_spectral.h
+    "gs_spectral_struct_bytes": (c_size_t, []),
+    "gs_spectral_block_width": (c_int32, [c_int32, c_int32]),
+    "gs_spectral_workspace_bytes": (c_size_t, [c_int32, c_int64, c_int32]),
+    "gs_spectral_validate": (ctypes.c_int, [ctypes.POINTER(GsSpectral)]),
+    "gs_spectral_svqb_host": (ctypes.c_int, [c_int32, c_void_p, c_void_p, c_void_p]),
+    "gs_spectral_ritz_host": (ctypes.c_int, [c_int32, c_void_p, c_void_p, c_void_p]),
+    "gs_spectral_embedding": (ctypes.c_int, [ctypes.POINTER(GsSpectral), c_void_p]),
     # include/gs_scene_loss.h
     "gs_scene_loss_struct_bytes": (c_size_t, []),
     "gs_scene_loss_workspace_bytes": (c_size_t, [c_int64]),

@@ -79,6 +79,8 @@ SOURCES = {
     "gs_feature_decoder.hip": ["-ffp-contract=off"],  # the epilogue (acc + bias) - target rounds as written, as the twin's
     "gs_feature_pca.hip": ["-ffp-contract=off"],  # x / norm - shift and the projection's products round as written, as the twins'
     "gs_feature_knn.hip": ["-ffp-contract=off"],  # the norm's squares and the exact similarities round as written, as the twin's
+    # the SpMM's products, the Gram sums and the residuals round as written: no contraction
+    "gs_spectral.hip": ["-ffp-contract=off"],
     "gs_api.hip": [],
     "gs_host.cpp": [],  # host-only C++ (also built by oracle/Makefile's sanitizer target)
     "gs_densify_host.cpp": [],  # host-only C++ (also built into tools/densify_host_sanitize.c's program)
@@ -103,6 +105,8 @@ SOURCES = {
     "gs_feature_pca_host.cpp": [],
     # host-only C++ (also built into tools/feature_knn_host_sanitize.c's program)
     "gs_feature_knn_host.cpp": [],
+    # host-only C++ (also built into tools/spectral_host_sanitize.c's program)
+    "gs_spectral_host.cpp": [],
 }
 COMMON = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall",
           "-Wno-unused-function", "-I", CSRC, "-I", INCLUDE]

@@ -574,20 +574,31 @@ def init_motion_bases_from_tracks(tracks: torch.Tensor, visibles: Optional[torch
 
 
 def init_motion_coefs_from_features(means: torch.Tensor, feats: torch.Tensor, num_bases: int, *, num_frames: int,
-                                    kmeans_iters: int = 10, seed: int = 0):
+                                    kmeans_iters: int = 10, seed: int = 0, cluster: str = "kmeans", knn: int = 20):
     """(bases, motion_coefs (N, K), labels (N,), centers (K, 3)) from the Gaussians' semantic
-    features, after feature_bases (motion_utils.py:122-162): k-means on the L2-normalised feats
+    features, after feature_bases (motion_utils.py:122-162): labels from a clustering of feats
     (N, F), per-cluster medians of means (N, 3), motion_coefs = 10 exp(-|mean - centre|) and
-    identity 6-D bases of (num_bases, num_frames).  An empty cluster's centre is NaN, as its median
-    is.  float32 device tensors run the HIP kernels; anything else takes the _torch twins."""
+    identity 6-D bases of (num_bases, num_frames).  cluster="kmeans" (the default) is k-means on
+    the L2-normalised feats; cluster="spectral" is the reference's own similarity_mapping, a
+    spectral clustering of the features' cosine affinity, here on the exact `knn`-neighbour graph
+    (spectral.spectral_clustering) in place of the dense N x N matrix.  An empty cluster's centre
+    is NaN, as its median is.  float32 device tensors run the HIP kernels; anything else takes the
+    _torch twins."""
     _check_points(means, "means", 3)
     _check_points(feats, "feats")
     if feats.shape[0] != means.shape[0]:
         raise ValueError(f"feats must have {means.shape[0]} rows (got {feats.shape[0]})")
     if int(num_frames) < 1:
         raise ValueError(f"num_frames must be >= 1 (got {num_frames})")
+    if cluster not in ("kmeans", "spectral"):
+        raise ValueError(f"cluster must be 'kmeans' or 'spectral' (got {cluster!r})")
     K = int(num_bases)
-    km = kmeans(F.normalize(feats.detach(), dim=-1).contiguous(), K, iters=kmeans_iters, seed=seed)
+    if cluster == "spectral":
+        from . import spectral  # spectral imports this module
+        km = spectral.spectral_clustering(feats.detach().contiguous(), K, knn=int(knn), kmeans_iters=kmeans_iters,
+                                          seed=seed)
+    else:
+        km = kmeans(F.normalize(feats.detach(), dim=-1).contiguous(), K, iters=kmeans_iters, seed=seed)
     centers = cluster_medians(means.detach(), km.labels, K)
     coefs = coefs_from_centers(means.detach().contiguous(), centers.contiguous())
     ident = torch.tensor([1.0, 0.0, 0.0, 0.0, 1.0, 0.0], dtype=torch.float32, device=means.device)
